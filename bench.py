@@ -11,7 +11,13 @@ gradient all-reduce overlapped) + optimizer step — the reference hot loop (tas
 W untimed warmup steps, then exactly K steps bracketed by barrier + device sync on both
 sides; the reported time is the MAX over ranks.
 
-Single GPU:   python bench.py --gpus 1 --steps 20 --warmup 5
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps,
+with ``--dump-outputs DIR`` one more untimed call of the timed step from the run's initial state
+whose loss and buffers are written, one JSON line.  ``--full`` adds
+the extra timed runs in the same process (the headline again in deterministic mode as
+'deterministic_variant', the reference's config of record as 'reference_config').
+
+Single GPU:   python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
 Multi GPU:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                   --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
           or  python bench.py --gpus N ...   (no WORLD_SIZE in the env: this process spawns the
@@ -91,18 +97,39 @@ def parse():
                     help="directory: each rank saves its final parameters and buffers there")
     ap.add_argument("--save-tune", default=None,
                     help="write the tuning table after the warm-up steps (JSON)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the extra timed configs in this process "
+                         "(see --reference-config, --time-deterministic); without it only the "
+                         "headline is set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, put model and optimizer back into the run's "
+                         "initial state, call the timed step once more (untimed; the same graph "
+                         "replay, kernels and plans) on batch 0, and have rank 0 write the loss "
+                         "it returns and the buffers (BatchNorm statistics) it leaves as "
+                         "DIR/loss.npy and DIR/buffers.npy, float32.  Same arguments: same "
+                         "inputs; outputs equal up to the rounding of float atomics and plan "
+                         "choice (measured: 4e-4 and 7e-4 relative for ResNet-50).  Parameters "
+                         "and gradients are not written: one bf16 ResNet-50 step does not "
+                         "reproduce them from run to run "
+                         "(profiles/dump_outputs_step_noise.txt)")
     ap.add_argument("--reference-config", default="auto", choices=["auto", "on", "off"],
-                    help="also time the reference's config of record in the same process "
-                         "(ResNet-18 32x32, 1000 classes, fp32, deterministic, --ref-batch per "
-                         "GPU) and report it as 'reference_config' in the JSON line; auto = with "
-                         "the default mipipe ResNet-50 headline on the GPU")
+                    help="with --full: also time the reference's config of record in the same "
+                         "process (ResNet-18 32x32, 1000 classes, fp32, deterministic, --ref-batch "
+                         "per GPU) and report it as 'reference_config' in the JSON line; auto = "
+                         "with the default mipipe ResNet-50 headline on the GPU")
     ap.add_argument("--time-deterministic", default="auto", choices=["auto", "on", "off"],
-                    help="also time the headline in deterministic mode (the reference's "
-                         "cudnn.deterministic=True, task.py:25) and report it as "
+                    help="with --full: also time the headline in deterministic mode (the "
+                         "reference's cudnn.deterministic=True, task.py:25) and report it as "
                          "'deterministic_variant'; auto = together with the reference config")
     ap.add_argument("--ref-batch", type=int, default=1024,
                     help="per-process batch of the reference config (task.py:58,153: 1024)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full and "on" in (a.reference_config, a.time_deterministic):
+        ap.error("--reference-config on / --time-deterministic on are extra timed runs: "
+                 "they need --full")
+    if a.steps < 1:
+        ap.error("--steps: at least one timed step")
+    return a
 
 
 def _heartbeat(every_s: float = 30.0) -> None:
@@ -183,7 +210,7 @@ def main() -> int:
         # no float atomics, fixed-order reductions, shipped plan tables), same discipline
         import copy
         b = copy.copy(a)
-        b.deterministic, b.dump_params, b.save_tune = 1, None, None
+        b.deterministic, b.dump_params, b.save_tune, b.dump_outputs = 1, None, None, None
         del r["model"]
         if not cpu:
             torch.cuda.empty_cache()
@@ -204,7 +231,7 @@ def main() -> int:
         b = copy.copy(a)
         b.model, b.res, b.classes, b.dtype, b.deterministic = "resnet18", 32, 1000, "fp32", 1
         b.batch = a.ref_batch
-        b.emulate_ranks, b.dump_params, b.save_tune = 1, None, None
+        b.emulate_ranks, b.dump_params, b.save_tune, b.dump_outputs = 1, None, None, None
         r.pop("model", None)
         if rd is not None:  # the deterministic variant's DDP model and buckets: gone too
             rd.pop("model", None)
@@ -264,7 +291,7 @@ def main() -> int:
 
 
 def _want_det_variant(a, cpu: bool) -> bool:
-    if a.time_deterministic == "off" or a.deterministic:
+    if not a.full or a.time_deterministic == "off" or a.deterministic:
         return False
     if a.time_deterministic == "on":
         return True
@@ -272,7 +299,7 @@ def _want_det_variant(a, cpu: bool) -> bool:
 
 
 def _want_reference_config(a, cpu: bool) -> bool:
-    if a.reference_config == "off":
+    if not a.full or a.reference_config == "off":
         return False
     if a.reference_config == "on":
         return True
@@ -302,9 +329,9 @@ def _run(a, world, rank, local, dev, distributed, cpu):
     if a.batch is None:
         a.batch = 32 if is_bert else 256
     if is_bert:
-        step, model, batches = build_bert(a, world, local, dev, rank)
+        step, model, batches, reset = build_bert(a, world, local, dev, rank)
     else:
-        step, model, batches = build_cnn(a, world, local, dev, rank)
+        step, model, batches, reset = build_cnn(a, world, local, dev, rank)
 
     model.train()
     for i in range(a.warmup):
@@ -343,9 +370,72 @@ def _run(a, world, rank, local, dev, distributed, cpu):
         torch.save({"params": [p.detach().cpu() for p in inner.parameters()],
                     "buffers": [b.detach().cpu() for b in inner.buffers()]},
                    os.path.join(a.dump_params, f"rank{rank}.pt"))
+    final_loss = float(loss.detach().float().item())
+    if a.dump_outputs:
+        # One more call of the timed step (the same callable: graph replay, this run's kernel
+        # mode and plans), after the clock has stopped, from the state the run started in and
+        # on batch 0, so that its inputs are the same in every run.  Where the timed steps
+        # themselves end is not: SGD at lr 0.1 amplifies their rounding differences within a
+        # few steps (profiles/dump_outputs_step_noise.txt).
+        reset()
+        out = step(*batches[0])
+        _sync(dev)
+        if rank == 0:
+            _dump_outputs(a.dump_outputs, out, getattr(model, "module", model))
     return {"value": a.batch * world * a.steps / dt, "dt": dt,
-            "loss": float(loss.detach().float().item()), "clocks": sampler.summary(),
+            "loss": final_loss, "clocks": sampler.summary(),
             "native_reducer": bool(getattr(model, "native_reducer", False)), "model": model}
+
+
+DUMP_SAMPLE = 2_000_000  # elements kept per dumped array (8 MB as float32)
+
+
+def _initial_state(a, model):
+    """Copy of the new model's weights and buffers (on the host), kept only for --dump-outputs."""
+    if not a.dump_outputs:
+        return None
+    return {k: v.detach().clone() for k, v in model.state_dict().items()}
+
+
+def _make_reset(model, opt, init):
+    """reset(): put model and optimizer back, IN PLACE (captured hipGraphs keep their addresses),
+    into the state this run started from: the weights and buffers saved in ``init``, dropout
+    step counters at zero, a new optimizer's state."""
+    def reset():
+        inner = getattr(model, "module", model)
+        inner.load_state_dict(init)
+        if hasattr(opt, "reset_state"):  # mipipe's flat optimizers
+            from mipipe.models import reset_step_counters
+            reset_step_counters(inner)
+            opt.reset_state()
+        else:  # torch.optim: zeroed state tensors are a new optimizer's (step 0, no momentum)
+            for st in opt.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+    return reset
+
+
+def _dump_outputs(path, loss, model) -> None:
+    """What one call of the timed step returns and leaves that is a stable function of its
+    inputs (profiles/dump_outputs_step_noise.txt): the loss, and the buffers (BatchNorm running
+    statistics) flattened in module order, as float32 ``path/<name>.npy``; an array of more than
+    DUMP_SAMPLE elements is cut to a fixed sample (sorted indices drawn from seed 0 for that
+    length)."""
+    import numpy as np
+
+    def flat(tensors):
+        parts = [t.detach().float().reshape(-1).cpu() for t in tensors]
+        v = torch.cat(parts).numpy() if parts else np.zeros(0, np.float32)
+        if v.size > DUMP_SAMPLE:
+            v = v[np.sort(np.random.default_rng(0).choice(v.size, DUMP_SAMPLE, replace=False))]
+        return np.ascontiguousarray(v, dtype=np.float32)
+
+    arrays = {"loss": loss.detach().float().reshape(-1).cpu().numpy(),
+              "buffers": flat(model.buffers())}
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def build_bert(a, world, local, dev, rank):
@@ -384,7 +474,9 @@ def build_bert(a, world, local, dev, rank):
         from mipipe.parallel import DistributedDataParallel
         drop = {} if a.bert_dropout is None else {
             "hidden_dropout_prob": a.bert_dropout, "attention_probs_dropout_prob": a.bert_dropout}
-        model = create_model(a.model, **drop).to(dev)
+        model = create_model(a.model, **drop)
+        init = _initial_state(a, model)
+        model = model.to(dev)
         model.compute_dtype = _compute_dtype(a)
         if a.distributed:
             model = DistributedDataParallel(model, device_ids=[local], bucket_cap_mb=a.bucket_cap_mb,
@@ -442,7 +534,9 @@ def build_bert(a, world, local, dev, rank):
                     return gs.replay(ids_of[id(ids)])
     else:
         from mipipe.models.reference import ref_bert
-        model = ref_bert(a.model).to(dev)
+        model = ref_bert(a.model)
+        init = _initial_state(a, model)
+        model = model.to(dev)
         if world > 1:
             model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local])
         opt = torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=0.01, fused=True)
@@ -456,7 +550,7 @@ def build_bert(a, world, local, dev, rank):
             loss.backward()
             opt.step()
             return loss
-    return step, model, batches
+    return step, model, batches, _make_reset(model, opt, init)
 
 
 def _capture(GraphedStep, step, batches, a):
@@ -527,7 +621,9 @@ def build_cnn(a, world, local, dev, rank):
         from mipipe.parallel import DistributedDataParallel
         from mipipe.train.task import CrossEntropyLoss
         cross_entropy = CrossEntropyLoss()  # also sums GoogLeNet / Inception-v3 aux losses
-        model = create_model(a.model, num_classes=a.classes).to(dev)
+        model = create_model(a.model, num_classes=a.classes)
+        init = _initial_state(a, model)
+        model = model.to(dev)
         model.compute_dtype = _compute_dtype(a)
         if a.distributed:
             model = DistributedDataParallel(model, device_ids=[local], bucket_cap_mb=a.bucket_cap_mb,
@@ -598,6 +694,7 @@ def build_cnn(a, world, local, dev, rank):
         # BASELINE.md); default NCHW for the zoo (MIOpen's NHWC depthwise / grouped convs are
         # several times slower than its NCHW ones)
         cl = a.model in _RESNET_CFG
+        init = _initial_state(a, model)
         model = model.to(dev).to(memory_format=torch.channels_last if cl else torch.contiguous_format)
         if world > 1:
             model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local])
@@ -626,7 +723,7 @@ def build_cnn(a, world, local, dev, rank):
             opt.step()
             return loss
 
-    return step, model, batches
+    return step, model, batches, _make_reset(model, opt, init)
 
 
 if __name__ == "__main__":

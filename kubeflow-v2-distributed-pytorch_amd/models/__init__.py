@@ -50,6 +50,18 @@ def create_model(arch: str, **kw):
     return _REGISTRY[arch](**kw)
 
 
+def reset_step_counters(model) -> None:
+    """Every module's per-step dropout seed counter (host ``_step``, device ``_step_dev``) back
+    to zero, in place: the next training forward draws the masks of a new model's first step,
+    also when it replays from a captured hipGraph."""
+    import torch
+    for m in model.modules():
+        if isinstance(getattr(m, "_step", None), int):
+            m._step = 0
+        if torch.is_tensor(getattr(m, "_step_dev", None)):
+            m._step_dev.zero_()
+
+
 def find_pretrained(arch: str, path: Optional[str] = None) -> Optional[str]:
     """Locate a torchvision-format weights file for ``arch`` without network access: ``path``
     when given, else torchvision's download cache ``$TORCH_HOME/hub/checkpoints/<arch>-*.pth``

@@ -79,6 +79,16 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _after_load(self) -> None:
         pass
 
+    def reset_state(self) -> None:
+        """Back to a new optimizer's state, in place: the flat state buffers are zeroed and the
+        compute shadow is re-derived from the (possibly reloaded) parameters.  Nothing is
+        reallocated, so a step captured into a hipGraph goes on working; its SGD kernel was
+        captured as a later step (``buf = m*buf + g``), which on a zero buffer is the first
+        step's ``buf = g``."""
+        for t in self.__dict__.get("_flat", {}).values():
+            t.zero_()
+        self.space.refresh_shadow()
+
 
 class SGD(_FlatOptimizer):
     def __init__(self, params, lr: float = 0.1, momentum: float = 0.0, dampening: float = 0.0,
@@ -95,6 +105,10 @@ class SGD(_FlatOptimizer):
     def _after_load(self) -> None:
         if any("momentum_buffer" in self.state[p] for p in self.params):
             self._steps = max(self._steps, 1)
+
+    def reset_state(self) -> None:
+        super().reset_state()
+        self._steps = 0
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0):
@@ -134,6 +148,12 @@ class AdamW(_FlatOptimizer):
                 self._step = int(s.item() if torch.is_tensor(s) else s)
                 break
         self._t_dev = None  # re-seeded from the loaded count at the next step
+
+    def reset_state(self) -> None:
+        super().reset_state()
+        self._step = 0
+        if self._t_dev is not None:
+            self._t_dev.zero_()  # in place: captured steps advance this very tensor
 
     def sync_step(self) -> int:
         """Host view of the step count (after graph replays the device counter is ahead)."""

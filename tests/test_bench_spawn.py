@@ -168,11 +168,96 @@ def test_bench_world4_gloo_bert_matches_emulated_ranks(tmp_path):
         assert torch.allclose(a, b, rtol=1e-5, atol=1e-6), (a - b).abs().max()
 
 
+def _dump(d):
+    import numpy as np
+    assert sorted(os.listdir(d)) == ["buffers.npy", "loss.npy"]
+    out = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    for v in out.values():
+        assert v.dtype == np.float32 and v.ndim == 1 and v.size > 0 and np.isfinite(v).all()
+    return out
+
+
+def test_bench_dump_outputs_is_first_step_and_plain_run_is_lean(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps the run is put back into its initial state and
+    the timed step is called once more on batch 0; the loss it returns and the buffers it leaves
+    are written as float32 .npy files.  Checked against an independent value: a run of ONE timed
+    step without warm-up reports that very step as final_loss and (--dump-params) leaves its
+    buffers, and the single-threaded CPU kernels are exact, so the dump must equal both; a run
+    with other --steps / --warmup writes the same dump, and its own final_loss is untouched by
+    the extra call.  A plain run (no `--full`) times the headline only, and asking for an extra
+    timed run without `--full` is an error, not a silent no-op."""
+    import numpy as np
+    import torch
+    outs, lines = [], []
+    for d, steps, warm in ((tmp_path / "a", 1, 0), (tmp_path / "b", 3, 1)):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--dump-outputs", str(d),
+                            "--dump-params", str(tmp_path / f"p{steps}")] + CPU_ARGS
+                           + ["--steps", str(steps), "--warmup", str(warm)], env=_env(),
+                           capture_output=True, text=True, timeout=300, cwd="/tmp")
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = _json_lines(r.stdout)[0]
+        assert j["steps"] == steps and j["ms_per_step"] > 0
+        assert "reference_config" not in j and "deterministic_variant" not in j
+        outs.append(_dump(d))
+        lines.append(j)
+    first = torch.load(tmp_path / "p1" / "rank0.pt", weights_only=True)
+    assert float(outs[0]["loss"][0]) == np.float32(lines[0]["final_loss"])
+    assert np.array_equal(outs[0]["buffers"],
+                          torch.cat([b.float().reshape(-1) for b in first["buffers"]]).numpy())
+    for f, v in outs[0].items():
+        assert np.array_equal(v, outs[1][f]), f
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1"] + CPU_ARGS
+                       + ["--steps", "3", "--warmup", "1"], env=_env(),
+                       capture_output=True, text=True, timeout=300, cwd="/tmp")
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert _json_lines(r.stdout)[0]["final_loss"] == lines[1]["final_loss"] != lines[0]["final_loss"]
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--reference-config", "on"]
+                       + CPU_ARGS, env=_env(), capture_output=True, text=True, timeout=120,
+                       cwd="/tmp")
+    assert r.returncode == 2 and "--full" in r.stderr and _json_lines(r.stdout) == []
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_is_the_timed_step_gpu(tmp_path):
+    """On the GPU the dump comes from the timed callable itself: the hipGraph replay with the
+    run's float-atomic kernels and tuned plans, after the reset to the initial state.  The
+    independent value is a second process that runs ONE eager step (--graph off, heuristic
+    plans, no warm-up) from the same seed: its final_loss is that first step's loss and its dump
+    repeats it.  Neither is bit-reproducible (atomics), so they are compared to one bf16 ulp
+    (2^-8 relative): the loss is a mean over 64 samples of values computed through bf16
+    activations whose roundings (2^-9 each) are independent, and the BatchNorm statistics are
+    fp32 means of such activations, compared in relative L2 norm."""
+    import numpy as np
+    R18 = ["--model", "resnet18", "--res", "32", "--batch", "64", "--gpus", "1"]
+    outs, lines = [], []
+    for d, extra in ((tmp_path / "g", ["--steps", "2", "--warmup", "1"]),
+                     (tmp_path / "e", ["--steps", "1", "--warmup", "0", "--graph", "off",
+                                       "--tune", "0"])):
+        r = subprocess.run([sys.executable, BENCH, "--dump-outputs", str(d)] + R18 + extra,
+                           env=_env(), capture_output=True, text=True, timeout=240, cwd="/tmp")
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_json_lines(r.stdout)[0])
+        outs.append(_dump(d))
+    assert lines[0]["config"]["hip_graph"] is True and lines[0]["config"]["deterministic"] is False
+    assert lines[1]["config"]["hip_graph"] is False
+    ulp = 2.0 ** -8
+    first = lines[1]["final_loss"]
+    print("first eager step", first, "dumped: graph", outs[0]["loss"], "eager", outs[1]["loss"])
+    assert abs(float(outs[0]["loss"][0]) - first) <= ulp * first
+    assert abs(float(outs[1]["loss"][0]) - first) <= ulp * first
+    g, e = outs[0]["buffers"].astype(np.float64), outs[1]["buffers"].astype(np.float64)
+    rel = np.linalg.norm(g - e) / np.linalg.norm(e)
+    print("buffers relative L2 distance", rel)
+    assert g.shape == e.shape and rel <= ulp
+    # the step really ran: BatchNorm running means left 0, running variances left 1
+    assert np.count_nonzero((g != 0) & (g != 1)) > g.size // 2
+
+
 def test_bench_reference_config_block_gloo():
-    """`--reference-config on` times the reference's config of record (ResNet-18 32x32, 1000
-    classes, fp32, deterministic) after the headline in the same process (and, here, under a
-    2-rank gloo DDP), and reports it inside the ONE JSON line."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--reference-config", "on",
+    """`--full --reference-config on` times the reference's config of record (ResNet-18 32x32,
+    1000 classes, fp32, deterministic) after the headline in the same process (and, here, under
+    a 2-rank gloo DDP), and reports it inside the ONE JSON line."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--reference-config", "on",
                         "--time-deterministic", "on", "--ref-batch", "4"] + CPU_ARGS, env=_env(),
                        capture_output=True, text=True, timeout=600, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]

@@ -9,9 +9,9 @@ timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 tail -3 $O/g_cpf_tests.txt
 [ $rc -eq 0 ] || exit 1
 for r in 1 2; do
-  timeout -k 10 400 python bench.py > $O/g_cpf_on_$r.json 2>$O/g_cpf_on_$r.err || exit 1
+  timeout -k 10 400 python bench.py --full > $O/g_cpf_on_$r.json 2>$O/g_cpf_on_$r.err || exit 1
   tail -1 $O/g_cpf_on_$r.json | cut -c1-200
-  MIPIPE_PREFETCH=0 timeout -k 10 400 python bench.py > $O/g_cpf_off_$r.json 2>$O/g_cpf_off_$r.err || exit 1
+  MIPIPE_PREFETCH=0 timeout -k 10 400 python bench.py --full > $O/g_cpf_off_$r.json 2>$O/g_cpf_off_$r.err || exit 1
   tail -1 $O/g_cpf_off_$r.json | cut -c1-200
 done
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/p_cpf_r50 -o run -- python bench.py --steps 5 --warmup 3 --reference-config off --time-deterministic off > $O/p_cpf_r50.log 2>&1 || exit 1

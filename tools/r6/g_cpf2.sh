@@ -10,7 +10,7 @@ tail -2 $O/g_cpf2_tests.txt
 [ $rc -eq 0 ] || exit 1
 for r in 1 2; do
   for c in 1 0; do
-    MIPIPE_CONV_PREFETCH=$c timeout -k 10 400 python bench.py > $O/g_cpf2_$c.$r.json 2>$O/g_cpf2_$c.$r.err || exit 1
+    MIPIPE_CONV_PREFETCH=$c timeout -k 10 400 python bench.py --full > $O/g_cpf2_$c.$r.json 2>$O/g_cpf2_$c.$r.err || exit 1
     python -c "import json;d=json.loads(open('$O/g_cpf2_$c.$r.json').read().strip().splitlines()[-1]);print('conv_pf=$c', d['value'], d['deterministic_variant']['value'], d['reference_config']['value'])"
   done
 done

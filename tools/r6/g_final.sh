@@ -11,7 +11,7 @@ echo "full rc=$?"
 tail -3 $O/f3_full.txt
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/f3_smoke.txt 2>&1 || exit 1
 echo smoke ok
-timeout -k 10 600 python -u bench.py > $O/f3_bench.jsonl 2> $O/f3_bench.err || exit 1
+timeout -k 10 600 python -u bench.py --full > $O/f3_bench.jsonl 2> $O/f3_bench.err || exit 1
 cut -c1-300 $O/f3_bench.jsonl
 timeout -k 10 300 python -u bench.py --model bert_base --seq 128 > $O/f3_bert.jsonl 2> $O/f3_bert.err || exit 1
 cut -c1-300 $O/f3_bert.jsonl
