@@ -1477,6 +1477,40 @@ std::tuple<Tensor, Tensor> synthetic_batch(Tensor idx, int C, int H, int W, int 
   return {x, lab};
 }
 
+// The record loader's crop / flip / normalise on the device: rec [n, label_bytes + C*H*W] uint8
+// whole records, idx [n] int64 sample indices, affine [2, C] fp32 -> (x [n,C,H,W], y [n] int64).
+std::tuple<Tensor, Tensor> record_decode(Tensor rec, Tensor idx, Tensor affine, int64_t C,
+                                         int64_t H, int64_t W, uint64_t seed, int64_t epoch,
+                                         int64_t pad, bool flip, bool train, int64_t label_bytes,
+                                         at::ScalarType dtype) {
+  check_cuda(rec, "rec");
+  check_cuda(idx, "idx");
+  check_f32(affine, "affine");
+  c10::DeviceGuard g(rec.device());
+  TORCH_CHECK(rec.scalar_type() == at::kByte, "rec must be uint8, got ", rec.scalar_type());
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64, got ", idx.scalar_type());
+  TORCH_CHECK(idx.device() == rec.device() && affine.device() == rec.device(),
+              "rec, idx and affine must be on one device");
+  const bool bf = dtype == at::kBFloat16;
+  TORCH_CHECK(bf || dtype == at::kFloat, "record_decode produces fp32 or bf16");
+  TORCH_CHECK(C >= 1 && H >= 1 && W >= 1 && C * H * W < (1ll << 31), "bad image shape");
+  TORCH_CHECK(label_bytes >= 1 && label_bytes <= 8, "label_bytes must be in [1, 8]");
+  TORCH_CHECK(pad >= 0 && pad < (1 << 20), "bad pad ", pad);
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == label_bytes + C * H * W, "rec must be [n, ",
+              label_bytes + C * H * W, "] (label bytes + C*H*W)");
+  const int64_t n = rec.size(0);
+  TORCH_CHECK(idx.dim() == 1 && idx.size(0) == n, "idx must be [n]");
+  TORCH_CHECK(affine.dim() == 2 && affine.size(0) == 2 && affine.size(1) == C,
+              "affine must be [2, C]");
+  auto x = torch::empty({n, C, H, W}, rec.options().dtype(dtype));
+  auto y = torch::empty({n}, rec.options().dtype(at::kLong));
+  if (n == 0) return {x, y};
+  mipipe::record_decode(rec.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), affine.data_ptr<float>(),
+                        x.data_ptr(), bf, y.data_ptr<int64_t>(), n, (int)C, (int)H, (int)W,
+                        (int)label_bytes, seed, (uint64_t)epoch, (int)pad, flip, train, stream());
+  return {x, y};
+}
+
 // ------------------------------------------------------------------------------- transformer ops
 Tensor gelu_fwd(Tensor x) {
   check_bf16(x, "x");
@@ -2153,6 +2187,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("wd"), py::arg("step"), py::arg("grad_scale"), py::arg("step_dev") = py::none());
   m.def("nchw_to_nhwc", &nchw_to_nhwc);
   m.def("synthetic_batch", &synthetic_batch);
+  m.def("record_decode", &record_decode, py::arg("rec"), py::arg("idx"), py::arg("affine"),
+        py::arg("C"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("epoch"),
+        py::arg("pad"), py::arg("flip"), py::arg("train"), py::arg("label_bytes"),
+        py::arg("dtype"));
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
   m.def("gemm_gelu", &gemm_gelu, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(),

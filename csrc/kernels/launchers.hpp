@@ -378,6 +378,14 @@ void stem_wgrad_unpack(const float* dwp, float* g, int Co, int C, int K, const l
                        hipStream_t st);
 void synthetic_batch(const int64_t* idx, int n, int C, int H, int W, int classes, int seed,
                      void* x, bool bf16_out, int64_t* labels, hipStream_t st);
+// Record decode (records.hip): rec [n][label_bytes + C*H*W] uint8 whole records, idx [n] global
+// sample indices, affine [2][C] fp32 (scale row 1/(255 std), offset row -mean/std) ->
+// x [n][C][H][W] (fp32 or bf16), y [n] little-endian labels.  RecordLoader::fill's crop / flip /
+// normalise, bit for bit (the augmentation is a hash of seed, epoch and idx[s]; pad / flip as the
+// loader configures them: both off outside training).
+void record_decode(const uint8_t* rec, const int64_t* idx, const float* affine, void* x,
+                   bool bf16_out, int64_t* y, long n, int C, int H, int W, int label_bytes,
+                   uint64_t seed, uint64_t epoch, int pad, bool flip, bool train, hipStream_t st);
 // Fused ResNet stem on the packed input (stem.hip): conv 7x7/2 (packed K = 224, 64 channels,
 // 112 output columns) -> BN -> ReLU -> max-pool 3x3/2/1.
 //   stem_fwd_stats : shifted Σ, Σ² of bf16(y) per channel (conv recomputed, y not stored) ->

@@ -1,0 +1,140 @@
+// Record decode: the device side of the record loader (csrc/runtime/loader.cpp RecordLoader::fill).
+// Input: whole uint8 records ([label bytes][C planes of H*W uint8], any stride, nothing aligned)
+// as the loader's raw mode uploads them, plus the global sample indices.  Output: the cropped /
+// flipped / normalised NCHW batch (fp32 or bf16) and the int64 labels — element for element what
+// fill() writes: the augmentation is splitmix64 of (seed, epoch, sample index), padding pixels are
+// zero before the normalisation, and v * scale + offset is a rounded multiply followed by a
+// rounded add (the host build has no FMA), so the fp32 output equals the host loader's bit for bit.
+//
+// A streaming pass (1 B in, 4 or 2 B out per element): a block works on one sample, thread 0
+// derives (dy, dx, flip) once, consecutive lanes write consecutive V-element groups of an output
+// row (16 B per lane when W allows it, 8 B for bf16 rows of W % 4 == 0, else one element) and
+// the flip reverses the read side.
+#include "common.hpp"
+#include "launchers.hpp"
+
+namespace mipipe {
+
+namespace {
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+  x += 0x9e3779b97f4a7c15ull;
+  x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+  x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+
+// v * sc + off in two roundings like the host build (g++ -O2, no FMA).  hipcc contracts a
+// multiply and an add into v_fma_f32 by default — also through __fmul_rn / __fadd_rn, which are
+// plain operators in HIP — so contraction is switched off for this expression.
+__device__ __forceinline__ float scale_offset(float v, float sc, float off) {
+#pragma clang fp contract(off)
+  const float m = v * sc;
+  return m + off;
+}
+
+template <int V>
+__device__ __forceinline__ void store_row(float* p, const float* f) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
+  else p[0] = f[0];
+}
+template <int V>
+__device__ __forceinline__ void store_row(__bf16* p, const float* f) {
+  if constexpr (V == 8) *reinterpret_cast<uint4*>(p) = pack8(f);
+  else if constexpr (V == 4) *reinterpret_cast<uint2*>(p) = pack4(f);
+  else p[0] = (__bf16)f[0];  // round to nearest even
+}
+
+constexpr int kThreads = 256;
+
+template <class T, int V>
+__global__ __launch_bounds__(kThreads) void record_decode_kernel(
+    const uint8_t* __restrict__ rec, const int64_t* __restrict__ idx,
+    const float* __restrict__ affine, T* __restrict__ x, int64_t* __restrict__ y, long n, int C,
+    int H, int W, int label_bytes, long rec_bytes, uint64_t seed, uint64_t epoch, int pad,
+    int flip, int train, int parts) {
+  __shared__ int s_aug[3];
+  const int Wv = W / V;
+  const int items = C * H * Wv;  // V-element groups of one sample
+  const long per = (long)C * H * W;
+  const long units = n * parts;
+  for (long u = blockIdx.x; u < units; u += gridDim.x) {
+    const long s = u / parts;
+    const int part = (int)(u - s * parts);
+    const uint8_t* r = rec + s * rec_bytes;
+    if (threadIdx.x == 0) {
+      int dy = 0, dx = 0, fl = 0;
+      if (train) {
+        const uint64_t h = splitmix64(seed ^ splitmix64(epoch * 0x100000001b3ull ^ (uint64_t)idx[s]));
+        if (pad > 0) {
+          dy = (int)(h % (uint64_t)(2 * pad + 1)) - pad;
+          dx = (int)((h >> 16) % (uint64_t)(2 * pad + 1)) - pad;
+        }
+        fl = flip && ((h >> 40) & 1);
+      }
+      s_aug[0] = dy;
+      s_aug[1] = dx;
+      s_aug[2] = fl;
+      if (part == 0) {
+        int64_t label = 0;
+        for (int k = 0; k < label_bytes; ++k) label |= (int64_t)r[k] << (8 * k);
+        y[s] = label;
+      }
+    }
+    __syncthreads();
+    const int dy = s_aug[0], dx = s_aug[1], fl = s_aug[2];
+    const uint8_t* img = r + label_bytes;
+    T* xs = x + s * per;
+    for (int it = part * kThreads + (int)threadIdx.x; it < items; it += parts * kThreads) {
+      const int row = it / Wv;  // c * H + y
+      const int x0 = (it - row * Wv) * V;
+      const int c = row / H;
+      const int sy = row - c * H + dy;
+      const float sc = affine[c], off = affine[C + c];
+      const bool row_ok = sy >= 0 && sy < H;
+      const uint8_t* ip = img + ((long)c * H + sy) * W;
+      float f[V];
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const int xx = fl ? W - 1 - (x0 + j) : x0 + j;
+        const int sx = xx + dx;
+        const float v = (row_ok && sx >= 0 && sx < W) ? (float)ip[sx] : 0.f;
+        f[j] = scale_offset(v, sc, off);
+      }
+      store_row<V>(xs + (long)row * W + x0, f);
+    }
+    __syncthreads();  // s_aug is rewritten by the next unit
+  }
+}
+
+template <class T, int V>
+void launch(const uint8_t* rec, const int64_t* idx, const float* affine, void* x, int64_t* y,
+            long n, int C, int H, int W, int label_bytes, uint64_t seed, uint64_t epoch, int pad,
+            bool flip, bool train, hipStream_t st) {
+  const long items = (long)C * H * (W / V);
+  const int parts = (int)std::min<long>(32, (items + kThreads - 1) / kThreads);
+  const long units = n * parts;
+  const unsigned grid = (unsigned)std::min<long>(units, 1l << 20);
+  const long rec_bytes = (long)label_bytes + (long)C * H * W;
+  hipLaunchKernelGGL((record_decode_kernel<T, V>), dim3(grid), dim3(kThreads), 0, st, rec, idx,
+                     affine, (T*)x, y, n, C, H, W, label_bytes, rec_bytes, seed, epoch, pad,
+                     (int)flip, (int)train, parts);
+}
+
+}  // namespace
+
+void record_decode(const uint8_t* rec, const int64_t* idx, const float* affine, void* x,
+                   bool bf16_out, int64_t* y, long n, int C, int H, int W, int label_bytes,
+                   uint64_t seed, uint64_t epoch, int pad, bool flip, bool train, hipStream_t st) {
+  if (n <= 0) return;
+  if (bf16_out) {
+    if (W % 8 == 0) launch<__bf16, 8>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
+    else if (W % 4 == 0) launch<__bf16, 4>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
+    else launch<__bf16, 1>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
+  } else {
+    if (W % 4 == 0) launch<float, 4>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
+    else launch<float, 1>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
+  }
+}
+
+}  // namespace mipipe

@@ -58,7 +58,8 @@ PYBIND11_MODULE(_runtime, m) {
       .def_readwrite("seed", &LoaderConfig::seed)
       .def_readwrite("workers", &LoaderConfig::workers)
       .def_readwrite("prefetch", &LoaderConfig::prefetch)
-      .def_readwrite("drop_last", &LoaderConfig::drop_last);
+      .def_readwrite("drop_last", &LoaderConfig::drop_last)
+      .def_readwrite("raw", &LoaderConfig::raw);
 
   py::class_<RecordLoader>(m, "RecordLoader")
       .def(py::init<const LoaderConfig&>())
@@ -70,6 +71,13 @@ PYBIND11_MODULE(_runtime, m) {
       .def("next_into",
            [](RecordLoader& l, uintptr_t x, uintptr_t y) {
              return l.next(reinterpret_cast<float*>(x), reinterpret_cast<int64_t*>(y));
+           },
+           py::call_guard<py::gil_scoped_release>())
+      .def("record_bytes", &RecordLoader::record_bytes)
+      // raw mode: rec_ptr [batch, record_bytes] uint8 and idx_ptr [batch] int64 host buffers
+      .def("next_raw_into",
+           [](RecordLoader& l, uintptr_t rec, uintptr_t idx) {
+             return l.next_raw(reinterpret_cast<uint8_t*>(rec), reinterpret_cast<int64_t*>(idx));
            },
            py::call_guard<py::gil_scoped_release>());
 }

@@ -9,6 +9,8 @@
 // (a pinned host tensor, then one async H2D copy) with the GIL released.
 // Augmentation randomness is a pure function of (seed, epoch, sample index), so a resumed or
 // re-sharded run sees the same crops/flips for the same sample and epoch.
+// Raw mode (LoaderConfig::raw): the workers only gather — whole records and their global sample
+// indices go through the same ring, and the transform runs on the GPU (csrc/kernels/records.hip).
 #include "runtime.hpp"
 
 #include <fcntl.h>
@@ -56,11 +58,13 @@ RecordLoader::RecordLoader(const LoaderConfig& cfg) : cfg_(cfg) {
   }
   slot_x_.resize(cfg_.prefetch);
   slot_y_.resize(cfg_.prefetch);
+  slot_raw_.resize(cfg_.prefetch);
   slot_n_.assign(cfg_.prefetch, 0);
   slot_batch_.assign(cfg_.prefetch, -1);
   const size_t per = (size_t)cfg_.C * cfg_.H * cfg_.W;
   for (int s = 0; s < cfg_.prefetch; ++s) {
-    slot_x_[s].resize((size_t)cfg_.batch * per);
+    if (cfg_.raw) slot_raw_[s].resize((size_t)cfg_.batch * rec_bytes_);  // no float slots
+    else slot_x_[s].resize((size_t)cfg_.batch * per);
     slot_y_[s].resize(cfg_.batch);
   }
   for (int w = 0; w < std::max(1, cfg_.workers); ++w) threads_.emplace_back([this] { worker(); });
@@ -146,6 +150,20 @@ void RecordLoader::fill(int slot, int64_t b, const std::vector<int64_t>& idx, in
   slot_n_[slot] = n;
 }
 
+// raw mode: gather only — whole records (label bytes included) and their global indices
+void RecordLoader::fill_raw(int slot, int64_t b, const std::vector<int64_t>& idx) {
+  const int64_t i0 = b * cfg_.batch;
+  const int n = (int)std::min<int64_t>(cfg_.batch, (int64_t)idx.size() - i0);
+  uint8_t* ro = slot_raw_[slot].data();
+  int64_t* io = slot_y_[slot].data();
+  for (int s = 0; s < n; ++s) {
+    const int64_t gi = idx[i0 + s];
+    memcpy(ro + (size_t)s * rec_bytes_, record(gi), rec_bytes_);
+    io[s] = gi;
+  }
+  slot_n_[slot] = n;
+}
+
 void RecordLoader::worker() {
   std::unique_lock<std::mutex> g(mu_);
   while (true) {
@@ -160,7 +178,8 @@ void RecordLoader::worker() {
     const int64_t epoch = epoch_;
     ++busy_;
     g.unlock();
-    fill(slot, b, *idx, epoch);
+    if (cfg_.raw) fill_raw(slot, b, *idx);
+    else fill(slot, b, *idx, epoch);
     g.lock();
     --busy_;
     if (gen == gen_) slot_batch_[slot] = b;
@@ -169,6 +188,7 @@ void RecordLoader::worker() {
 }
 
 int RecordLoader::next(float* x, int64_t* y) {
+  if (cfg_.raw) throw std::logic_error("next on a raw-mode loader (use next_raw)");
   std::unique_lock<std::mutex> g(mu_);
   if (next_consume_ >= nbatches_) return 0;
   const int64_t b = next_consume_;
@@ -180,6 +200,26 @@ int RecordLoader::next(float* x, int64_t* y) {
   const size_t per = (size_t)cfg_.C * cfg_.H * cfg_.W;
   memcpy(x, slot_x_[slot].data(), (size_t)n * per * sizeof(float));
   memcpy(y, slot_y_[slot].data(), (size_t)n * sizeof(int64_t));
+  g.lock();
+  slot_batch_[slot] = -1;
+  ++next_consume_;
+  g.unlock();
+  cv_work_.notify_all();
+  return n;
+}
+
+int RecordLoader::next_raw(uint8_t* rec, int64_t* idx) {
+  if (!cfg_.raw) throw std::logic_error("next_raw needs LoaderConfig::raw");
+  std::unique_lock<std::mutex> g(mu_);
+  if (next_consume_ >= nbatches_) return 0;
+  const int64_t b = next_consume_;
+  const int slot = (int)(b % cfg_.prefetch);
+  cv_slot_.wait(g, [&] { return slot_batch_[slot] == b || shutdown_; });
+  if (shutdown_) return 0;
+  const int n = slot_n_[slot];
+  g.unlock();
+  memcpy(rec, slot_raw_[slot].data(), (size_t)n * rec_bytes_);
+  memcpy(idx, slot_y_[slot].data(), (size_t)n * sizeof(int64_t));
   g.lock();
   slot_batch_[slot] = -1;
   ++next_consume_;

@@ -96,6 +96,9 @@ struct LoaderConfig {
   int workers = 8;
   int prefetch = 4;
   bool drop_last = false;
+  // raw mode: workers only gather whole records (label bytes included) and their global sample
+  // indices; crop / flip / normalise run on the device (csrc/kernels/records.hip)
+  bool raw = false;
 };
 
 class RecordLoader {
@@ -106,19 +109,25 @@ class RecordLoader {
   void start_epoch(const std::vector<int64_t>& indices, int64_t epoch);
   // copies the next batch to x [n,C,H,W] f32 / y [n] i64; returns n (0 = epoch exhausted)
   int next(float* x, int64_t* y);
+  // raw mode: copies the next batch's records to rec [n, record_bytes] u8 and their global sample
+  // indices to idx [n] i64; returns n (0 = epoch exhausted)
+  int next_raw(uint8_t* rec, int64_t* idx);
+  size_t record_bytes() const { return rec_bytes_; }
   int64_t batches_per_epoch() const;
   const uint8_t* record(int64_t i) const;
 
  private:
   void worker();
   void fill(int slot, int64_t b, const std::vector<int64_t>& idx, int64_t epoch);
+  void fill_raw(int slot, int64_t b, const std::vector<int64_t>& idx);
   LoaderConfig cfg_;
   size_t rec_bytes_ = 0;
   std::vector<std::pair<const uint8_t*, size_t>> maps_;
   std::vector<int64_t> file_start_;
   int64_t total_ = 0;
   std::vector<std::vector<float>> slot_x_;
-  std::vector<std::vector<int64_t>> slot_y_;
+  std::vector<std::vector<int64_t>> slot_y_;  // labels; raw mode: sample indices
+  std::vector<std::vector<uint8_t>> slot_raw_;
   std::vector<int> slot_n_;
   std::vector<int64_t> slot_batch_;
   std::vector<int64_t> indices_;

@@ -7,7 +7,10 @@ files from a deterministic, learnable generator (:func:`write_synthetic_dataset`
 and *eval* steps read them through :class:`RecordDataLoader`, which drives the C++
 ``RecordLoader`` (csrc/runtime/loader.cpp: memory-mapped files, worker threads, RandomCrop
 (padding) + RandomHorizontalFlip + Normalize, ordered prefetch ring) and hands each batch to the
-GPU through a pinned staging buffer and one non-blocking copy.
+GPU through a pinned staging buffer and one non-blocking copy.  With ``decode="device"`` the
+loader threads only gather the uint8 records; those are uploaded as they are and the same
+transform runs on the GPU (csrc/kernels/records.hip), bit-identical to the host path.  Labels are
+1 byte as in CIFAR-10, or ``label_bytes`` (up to 8) little-endian bytes.
 
 :func:`reference_transform` is the plain-NumPy definition of the per-sample transform the
 native loader implements (tests compare the two bit-for-bit).
@@ -34,31 +37,55 @@ MNIST_STD = (0.3081,)
 _MASK64 = (1 << 64) - 1
 
 
-def write_records(path: str, images: np.ndarray, labels: np.ndarray) -> None:
-    """images uint8 [N, C, H, W], labels [N] (< 256) -> CIFAR-binary record file."""
+def _check_label_bytes(label_bytes: int) -> int:
+    if not 1 <= int(label_bytes) <= 8:
+        raise ValueError(f"label_bytes must be in [1, 8], got {label_bytes}")
+    return int(label_bytes)
+
+
+def write_records(path: str, images: np.ndarray, labels: np.ndarray, label_bytes: int = 1) -> None:
+    """images uint8 [N, C, H, W], labels [N] (< 256 ** label_bytes, stored little-endian) ->
+    CIFAR-binary record file (``label_bytes`` = 1 is the CIFAR-10 layout)."""
+    lb = _check_label_bytes(label_bytes)
     images = np.ascontiguousarray(images, dtype=np.uint8)
     n = images.shape[0]
-    rec = np.empty((n, 1 + images[0].size), dtype=np.uint8)
-    rec[:, 0] = np.asarray(labels, dtype=np.uint8)
-    rec[:, 1:] = images.reshape(n, -1)
+    labels = np.asarray(labels).astype(np.int64).reshape(n)
+    if n and (labels.min() < 0 or (lb < 8 and labels.max() >= 1 << (8 * lb))):
+        raise ValueError(f"labels do not fit {lb} byte(s)")
+    rec = np.empty((n, lb + int(np.prod(images.shape[1:]))), dtype=np.uint8)
+    for k in range(lb):
+        rec[:, k] = (labels >> (8 * k)) & 0xFF
+    rec[:, lb:] = images.reshape(n, -1)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     rec.tofile(path)
 
 
-def read_records(path: str, shape: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
+def _decode_labels(raw: np.ndarray, label_bytes: int) -> np.ndarray:
+    y = np.zeros(raw.shape[0], dtype=np.int64)
+    for k in range(label_bytes):
+        y |= raw[:, k].astype(np.int64) << (8 * k)
+    return y
+
+
+def read_records(path: str, shape: Sequence[int], label_bytes: int = 1
+                 ) -> Tuple[np.ndarray, np.ndarray]:
     C, H, W = shape
-    raw = np.fromfile(path, dtype=np.uint8).reshape(-1, 1 + C * H * W)
-    return raw[:, 1:].reshape(-1, C, H, W), raw[:, 0].astype(np.int64)
+    lb = _check_label_bytes(label_bytes)
+    raw = np.fromfile(path, dtype=np.uint8).reshape(-1, lb + C * H * W)
+    return raw[:, lb:].reshape(-1, C, H, W), _decode_labels(raw, lb)
 
 
 def write_synthetic_dataset(out_dir: str, name: str = "cifar10", n_train: int = 10000,
-                            n_test: int = 2000, seed: int = 0, num_classes: int = 10) -> dict:
+                            n_test: int = 2000, seed: int = 0, num_classes: int = 10,
+                            shape: Optional[Sequence[int]] = None, label_bytes: int = 1) -> dict:
     """Learnable synthetic dataset in CIFAR-binary layout: class template (low-frequency
-    pattern) + per-sample noise, quantised to uint8.  Returns a manifest dict."""
-    shape = {"cifar10": (3, 32, 32), "mnist": (1, 28, 28)}[name]
+    pattern) + per-sample noise, quantised to uint8.  ``shape`` (C, H, W) overrides the shape
+    ``name`` stands for.  Returns a manifest dict."""
+    shape = (tuple(int(v) for v in shape) if shape is not None
+             else {"cifar10": (3, 32, 32), "mnist": (1, 28, 28)}[name])
     C, H, W = shape
     rng = np.random.default_rng(seed)
-    base = rng.normal(0.0, 1.0, size=(num_classes, C, H // 4, W // 4))
+    base = rng.normal(0.0, 1.0, size=(num_classes, C, -(-H // 4), -(-W // 4)))
     templates = np.kron(base, np.ones((1, 1, 4, 4)))[:, :, :H, :W]
 
     def make(n, split_seed):
@@ -73,10 +100,10 @@ def write_synthetic_dataset(out_dir: str, name: str = "cifar10", n_train: int = 
     for split, n, s in (("train", n_train, 1), ("test", n_test, 2)):
         img, y = make(n, s)
         path = os.path.join(out_dir, f"{name}_{split}.bin")
-        write_records(path, img, y)
+        write_records(path, img, y, label_bytes=label_bytes)
         files[split] = path
     return {"name": name, "shape": list(shape), "num_classes": num_classes,
-            "n_train": n_train, "n_test": n_test, "files": files}
+            "label_bytes": int(label_bytes), "n_train": n_train, "n_test": n_test, "files": files}
 
 
 def dataset_files(data_dir: str, name: str, split: str) -> List[str]:
@@ -129,50 +156,76 @@ class RecordDataLoader:
     """Iterates (x [B,C,H,W] float32, y [B] int64) batches of this rank's shard.
 
     ``sampler`` follows :class:`DistributedSampler` semantics (``set_epoch`` reshuffles);
-    batches land on ``device`` (pinned staging + non_blocking copy for GPU devices)."""
+    batches land on ``device`` (pinned staging + non_blocking copy for GPU devices).
+
+    ``decode="host"`` (default): the loader's CPU threads crop / flip / normalise and the float32
+    batch is uploaded.  ``decode="device"``: the threads only gather the uint8 records (raw
+    mode), the records and their sample indices are uploaded (a quarter of the bytes) and
+    ``ops.kernels.record_decode`` runs the same transform on ``device`` — the same bits as the
+    host path.  ``out_dtype``: dtype of ``x`` (float32 or bfloat16).  ``label_bytes``: width of
+    the little-endian label in front of every record."""
 
     def __init__(self, files: Sequence[str], shape: Sequence[int], batch_size: int,
                  sampler: Optional[DistributedSampler] = None, train: bool = True,
                  pad: int = 4, flip: bool = True, mean=CIFAR10_MEAN, std=CIFAR10_STD,
                  seed: int = 0, workers: int = 8, prefetch: int = 4, drop_last: bool = False,
-                 device: Optional[torch.device] = None):
+                 device: Optional[torch.device] = None, decode: str = "host",
+                 out_dtype: torch.dtype = torch.float32, label_bytes: int = 1):
         from mipipe.runtime import runtime, runtime_available
+        if decode not in ("host", "device"):
+            raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
         self.shape = tuple(shape)
         self.batch_size = batch_size
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         self.train, self.pad, self.flip = train, pad, flip
         self.mean, self.std, self.seed = tuple(mean), tuple(std), seed
+        self.decode, self.out_dtype = decode, out_dtype
+        self.label_bytes = _check_label_bytes(label_bytes)
         self.epoch = 0
         self.files = list(files)
         self.native = runtime_available()
+        C, H, W = self.shape
+        self.record_bytes = self.label_bytes + C * H * W
         if self.native:
             cfg = runtime().LoaderConfig()
             cfg.files = self.files
             cfg.C, cfg.H, cfg.W = self.shape
             cfg.batch = batch_size
+            cfg.label_bytes = self.label_bytes
             cfg.train, cfg.pad, cfg.flip = train, pad if train else 0, flip and train
             cfg.mean, cfg.std = list(map(float, mean)), list(map(float, std))
             cfg.seed, cfg.workers, cfg.prefetch, cfg.drop_last = seed, workers, prefetch, drop_last
+            cfg.raw = decode == "device"
             self._ld = runtime().RecordLoader(cfg)
             n = len(self._ld)
         else:
-            self._imgs, self._labels = [], []
-            for f in self.files:
-                x, y = read_records(f, self.shape)
-                self._imgs.append(x)
-                self._labels.append(y)
-            self._imgs = np.concatenate(self._imgs) if self._imgs else np.zeros((0, *self.shape), np.uint8)
-            self._labels = np.concatenate(self._labels) if self._labels else np.zeros(0, np.int64)
+            raws = [np.fromfile(f, dtype=np.uint8).reshape(-1, self.record_bytes)
+                    for f in self.files]
+            self._raw = (np.concatenate(raws) if raws
+                         else np.zeros((0, self.record_bytes), np.uint8))
+            self._imgs = self._raw[:, self.label_bytes:].reshape(-1, C, H, W)
+            self._labels = _decode_labels(self._raw, self.label_bytes)
             n = len(self._labels)
         self.num_samples_total = n
         self.sampler = sampler if sampler is not None else DistributedSampler(n, shuffle=train,
                                                                                seed=seed)
         self.drop_last = drop_last
         pin = self.device.type == "cuda"
-        C, H, W = self.shape
-        self._stage = [(torch.empty(batch_size, C, H, W, dtype=torch.float32, pin_memory=pin),
-                        torch.empty(batch_size, dtype=torch.int64, pin_memory=pin))
-                       for _ in range(2)]
+        if decode == "device":
+            # the transform's constants, computed in float32 exactly as loader.cpp does
+            m32, s32 = np.asarray(self.mean, np.float32), np.asarray(self.std, np.float32)
+            affine = np.stack([np.float32(1.0) / (np.float32(255.0) * s32), -m32 / s32])
+            self._affine = torch.from_numpy(affine.astype(np.float32)).to(self.device)
+            self._stage = [(torch.empty(batch_size, self.record_bytes, dtype=torch.uint8,
+                                        pin_memory=pin),
+                            torch.empty(batch_size, dtype=torch.int64, pin_memory=pin))
+                           for _ in range(2)]
+        else:
+            self._stage = [(torch.empty(batch_size, C, H, W, dtype=torch.float32, pin_memory=pin),
+                            torch.empty(batch_size, dtype=torch.int64, pin_memory=pin))
+                           for _ in range(2)]
 
     def __len__(self) -> int:
         n = len(self.sampler)
@@ -185,7 +238,9 @@ class RecordDataLoader:
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         self.epoch = getattr(self.sampler, "epoch", self.epoch)  # follow sampler.set_epoch
         idx = list(iter(self.sampler))
-        if self.native:
+        if self.decode == "device":
+            yield from self._iter_device(idx)
+        elif self.native:
             self._ld.start_epoch(idx, self.epoch)
             k = 0
             events = [None, None]
@@ -201,7 +256,7 @@ class RecordDataLoader:
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream(self.device))
                     events[k % 2] = ev
-                yield out
+                yield self._cast(out)
                 k += 1
         else:
             for b in range(len(self)):
@@ -210,7 +265,47 @@ class RecordDataLoader:
                                                   self.train, self.pad if self.train else 0,
                                                   self.flip and self.train, self.mean, self.std)
                               for i in sl])
-                yield self._to_device(torch.from_numpy(x), torch.from_numpy(self._labels[sl]))
+                yield self._cast(self._to_device(torch.from_numpy(x),
+                                                 torch.from_numpy(self._labels[sl])))
+
+    def _iter_device(self, idx) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        """decode="device": upload the uint8 records + sample indices, transform on the device."""
+        from mipipe.ops import kernels as K
+        epoch = self.epoch
+
+        def decode(rec, gi):
+            return K.record_decode(rec, gi, self._affine, self.shape, self.seed, epoch,
+                                   self.pad if self.train else 0, self.flip and self.train,
+                                   self.train, self.label_bytes, self.out_dtype)
+
+        if not self.native:
+            for b in range(len(self)):
+                sl = idx[b * self.batch_size:(b + 1) * self.batch_size]
+                rec, gi = self._to_device(torch.from_numpy(self._raw[sl]),
+                                          torch.tensor(sl, dtype=torch.int64))
+                yield decode(rec, gi)
+            return
+        self._ld.start_epoch(idx, epoch)
+        k = 0
+        events = [None, None]
+        while True:
+            rs, gs = self._stage[k % 2]
+            if events[k % 2] is not None:
+                events[k % 2].synchronize()  # the H2D copies out of this staging pair are done
+            n = self._ld.next_raw_into(rs.data_ptr(), gs.data_ptr())
+            if n == 0:
+                return
+            rec, gi = self._to_device(rs[:n], gs[:n])
+            if self.device.type == "cuda":
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                events[k % 2] = ev
+            yield decode(rec, gi)
+            k += 1
+
+    def _cast(self, batch):
+        x, y = batch
+        return (x if x.dtype == self.out_dtype else x.to(self.out_dtype)), y
 
     def _to_device(self, x: torch.Tensor, y: torch.Tensor):
         if self.device.type == "cpu":

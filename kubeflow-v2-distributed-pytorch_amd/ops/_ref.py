@@ -496,3 +496,44 @@ def bn_relu_fold(y: Tensor, scale: Tensor, bias: Tensor) -> Tensor:
     """The operand a folded input BatchNorm hands its consumer conv: relu(y*scale + bias) per
     channel (NHWC), in y's dtype — the values bn_act_fwd would have stored."""
     return torch.relu(y.float() * scale.float() + bias.float()).to(y.dtype)
+
+
+def record_decode(rec: Tensor, idx: Tensor, affine: Tensor, shape, seed: int, epoch: int,
+                  pad: int, flip: bool, train: bool, label_bytes: int = 1,
+                  dtype=torch.float32) -> Tuple[Tensor, Tensor]:
+    """The record loader's transform on whole records (csrc/kernels/records.hip's contract):
+    ``rec`` uint8 [n, label_bytes + C*H*W], ``idx`` int64 [n] global sample indices, ``affine``
+    fp32 [2, C] (scale row, offset row) -> (x [n, C, H, W] ``dtype``, y [n] int64).  Per-sample
+    (dy, dx, flip) are splitmix64 of (seed, epoch, index) as in ``data.records``; the pixel is
+    zero outside the image, then ``v * scale`` and ``+ offset`` as two rounded fp32 operations."""
+    from mipipe.data.records import _MASK64, _splitmix64
+    C, H, W = shape
+    n = rec.shape[0]
+    dev = rec.device
+    y = torch.zeros(n, dtype=torch.int64, device=dev)
+    for k in range(label_bytes):
+        y |= rec[:, k].long() << (8 * k)
+    dy, dx, fl = [0] * n, [0] * n, [False] * n
+    if train:
+        for s, gi in enumerate(idx.tolist()):
+            h = _splitmix64(seed ^ _splitmix64(((epoch * 0x100000001B3) & _MASK64) ^ (gi & _MASK64)))
+            if pad > 0:
+                dy[s] = int(h % (2 * pad + 1)) - pad
+                dx[s] = int((h >> 16) % (2 * pad + 1)) - pad
+            fl[s] = bool(flip and ((h >> 40) & 1))
+    img = rec[:, label_bytes:].reshape(n, C, H, W).float()
+    padded = F.pad(img, (pad, pad, pad, pad))
+    ar_h = torch.arange(H, device=dev)
+    ar_w = torch.arange(W, device=dev)
+    rows = ar_h[None, :] + (torch.tensor(dy, device=dev, dtype=torch.long)[:, None] + pad)
+    flt = torch.tensor(fl, device=dev, dtype=torch.bool)[:, None]
+    cols = torch.where(flt, (W - 1 - ar_w)[None, :], ar_w[None, :]) \
+        + (torch.tensor(dx, device=dev, dtype=torch.long)[:, None] + pad)
+    out = padded[torch.arange(n, device=dev)[:, None, None, None],
+                 torch.arange(C, device=dev)[None, :, None, None],
+                 rows[:, None, :, None], cols[:, None, None, :]]
+    sc = affine[0].float().view(1, C, 1, 1)
+    off = affine[1].float().view(1, C, 1, 1)
+    x = out * sc
+    x = x + off
+    return x.to(dtype), y

@@ -20,7 +20,7 @@ __all__ = ["conv_fwd", "conv_dgrad", "conv_wgrad", "bn_finalize", "bn_act_fwd",
            "avgpool_fwd", "avgpool_bwd", "pool_bn_fwd", "pool_bn_bwd", "pool_bn_supported", "stem_fused_supported", "stem_fwd_stats",
            "stem_fwd_pool", "stem_bwd", "gemm", "cross_entropy_fwd_bwd", "top1_correct", "sgd_step",
            "adamw_step", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
-           "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "use_native",
+           "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "record_decode", "use_native",
            "gconv_fwd", "gconv_dgrad", "gconv_wgrad", "chan_stats", "affine_act",
            "bn_generic_bwd_reduce", "bn_generic_bwd_apply", "avgpool2d_fwd", "avgpool2d_bwd"]
 
@@ -560,8 +560,21 @@ def stem_pack(x, dtype, pad: int, Hp: int, Wsp: int, w=None):
     return y.contiguous().to(dtype)
 
 
+def record_decode(rec, idx, affine, shape, seed: int, epoch: int, pad: int, flip: bool,
+                  train: bool, label_bytes: int = 1, dtype=torch.float32):
+    """The record loader's crop / flip / normalise on whole uint8 records ``rec`` [n, label_bytes
+    + C*H*W] with global sample indices ``idx`` (int64 [n]) and ``affine`` fp32 [2, C] ->
+    (x [n, C, H, W] fp32 / bf16, y [n] int64): bit-identical to the host loader's output."""
+    C, H, W = (int(v) for v in shape)
+    if use_native(rec):
+        return native().record_decode(rec, idx, affine, C, H, W, int(seed), int(epoch), int(pad),
+                                      bool(flip), bool(train), int(label_bytes), dtype)
+    return _ref.record_decode(rec, idx, affine, (C, H, W), int(seed), int(epoch), int(pad),
+                              bool(flip), bool(train), int(label_bytes), dtype)
+
+
 # ----------------------------------------------------------------------------- vision.hip
-_ACT = {"none": 0, "relu": 1, "relu6": 2}
+_ACT ={"none": 0, "relu": 1, "relu6": 2}
 
 
 def gconv_fwd(x, w, stride, pad, groups, bias=None, act="none"):

@@ -183,6 +183,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="directory with CIFAR-binary record files (<dataset>_{train,test}.bin or "
                         "cifar-10-batches-bin/); read by the native loader. Empty: synthetic "
                         "on-device data")
+    p.add_argument("--device-decode", type=int, choices=[0, 1], default=0,
+                   help="with --data-dir: 1 uploads the uint8 records and crops / flips / "
+                        "normalises them on the device (same bits as the host loader's output)")
     p.add_argument("--train-samples", type=int, default=None)
     p.add_argument("--test-samples", type=int, default=None)
     p.add_argument("--num_classes", type=int, default=None,
@@ -369,15 +372,17 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         mean, std = ((REC.MNIST_MEAN, REC.MNIST_STD) if args.dataset == "mnist"
                      else (REC.CIFAR10_MEAN, REC.CIFAR10_STD))
         pad = 4 if args.dataset == "cifar10" else 0
+        decode = "device" if args.device_decode else "host"
         probe = REC.RecordDataLoader(train_files, (C, H, W), args.batch_size, train=True,
                                      pad=pad, mean=mean, std=std, seed=args.random_seed,
-                                     workers=max(1, args.workers), device=device)
+                                     workers=max(1, args.workers), device=device, decode=decode)
         train_sampler = DistributedSampler(probe.num_samples_total, seed=args.random_seed)
         probe.sampler = train_sampler
         train_loader = probe
         tfiles = test_files or train_files
         test_loader = REC.RecordDataLoader(tfiles, (C, H, W), 128, train=False, mean=mean,
-                                           std=std, workers=max(1, args.workers), device=device)
+                                           std=std, workers=max(1, args.workers), device=device,
+                                           decode=decode)
         test_sampler = DistributedSampler(test_loader.num_samples_total, shuffle=False)
         test_loader.sampler = test_sampler
     else:

@@ -1,0 +1,127 @@
+// Stand-alone stress program for the record loader's raw mode (csrc/runtime/loader.cpp), meant
+// to be built with a host sanitizer:
+//   g++ -std=c++17 -O1 -g -fsanitize=thread -Icsrc/runtime tools/loader_raw_stress.cpp \
+//       csrc/runtime/loader.cpp -o loader_raw_stress_tsan -lpthread
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined ... (same)
+// It writes two record files, then drives a raw-mode loader with several workers through
+// start_epoch generations — complete epochs, an epoch abandoned half way (the next generation
+// starts while workers are still filling slots) and a partial last batch — and checks every
+// byte and index that next_raw returns.  Exit status 0 = all checks passed.
+#include <unistd.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "runtime.hpp"
+
+using namespace mipipe_rt;
+
+static int g_fail = 0;
+#define CHECK(c)                                                   \
+  do {                                                             \
+    if (!(c)) {                                                    \
+      std::fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #c); \
+      ++g_fail;                                                    \
+    }                                                              \
+  } while (0)
+
+static uint8_t byte_of(int64_t rec, size_t k) { return (uint8_t)((rec * 131 + (int64_t)k * 7 + 3) & 0xFF); }
+
+static std::string write_file(int64_t first, int64_t count, size_t rec_bytes) {
+  char path[] = "/tmp/loader_raw_stress_XXXXXX";
+  int fd = mkstemp(path);
+  if (fd < 0) { std::perror("mkstemp"); std::exit(2); }
+  std::vector<uint8_t> buf((size_t)count * rec_bytes);
+  for (int64_t r = 0; r < count; ++r)
+    for (size_t k = 0; k < rec_bytes; ++k) buf[(size_t)r * rec_bytes + k] = byte_of(first + r, k);
+  if (write(fd, buf.data(), buf.size()) != (ssize_t)buf.size()) { std::perror("write"); std::exit(2); }
+  close(fd);
+  return path;
+}
+
+// consume up to max_batches batches (< 0: the whole epoch); returns the samples seen
+static int64_t consume(RecordLoader& ld, const std::vector<int64_t>& order, int batch,
+                       size_t rec_bytes, int max_batches) {
+  std::vector<uint8_t> rec((size_t)batch * rec_bytes);
+  std::vector<int64_t> idx(batch);
+  int64_t seen = 0;
+  for (int b = 0; max_batches < 0 || b < max_batches; ++b) {
+    const int n = ld.next_raw(rec.data(), idx.data());
+    if (n == 0) break;
+    CHECK(n == (int)std::min<int64_t>(batch, (int64_t)order.size() - seen));
+    for (int s = 0; s < n; ++s) {
+      const int64_t gi = order[seen + s];
+      CHECK(idx[s] == gi);
+      for (size_t k = 0; k < rec_bytes; ++k)
+        if (rec[(size_t)s * rec_bytes + k] != byte_of(gi, k)) {
+          CHECK(!"record byte mismatch");
+          break;
+        }
+    }
+    seen += n;
+  }
+  return seen;
+}
+
+int main() {
+  const int C = 3, H = 8, W = 8, label_bytes = 2, batch = 5;
+  const size_t rec_bytes = label_bytes + (size_t)C * H * W;
+  const int64_t n0 = 20, n1 = 17, total = n0 + n1;
+  LoaderConfig cfg;
+  cfg.files = {write_file(0, n0, rec_bytes), write_file(n0, n1, rec_bytes)};
+  cfg.label_bytes = label_bytes;
+  cfg.C = C; cfg.H = H; cfg.W = W;
+  cfg.batch = batch;
+  cfg.mean = {0.f, 0.f, 0.f};
+  cfg.stdv = {1.f, 1.f, 1.f};
+  cfg.workers = 6;
+  cfg.prefetch = 3;
+  cfg.raw = true;
+  {
+    RecordLoader ld(cfg);
+    CHECK(ld.size() == total);
+    CHECK(ld.record_bytes() == rec_bytes);
+    std::vector<int64_t> order(total);
+    std::iota(order.begin(), order.end(), 0);
+    for (int round = 0; round < 40; ++round) {
+      // a different permutation every generation
+      for (int64_t i = total - 1; i > 0; --i) std::swap(order[i], order[(i * 7919 + round * 31) % (i + 1)]);
+      ld.start_epoch(order, round);
+      CHECK(ld.batches_per_epoch() == (total + batch - 1) / batch);
+      if (round % 3 == 1) {
+        // abandon this epoch after two batches: the next start_epoch arrives mid-epoch
+        CHECK(consume(ld, order, batch, rec_bytes, 2) == 2 * batch);
+        continue;
+      }
+      if (round % 3 == 2) continue;  // a generation nobody consumes at all
+      CHECK(consume(ld, order, batch, rec_bytes, -1) == total);
+      std::vector<uint8_t> r(batch * rec_bytes);
+      std::vector<int64_t> ix(batch);
+      CHECK(ld.next_raw(r.data(), ix.data()) == 0);  // exhausted
+    }
+    // a rank's shard (odd samples, drop_last off) started right after a half-consumed epoch
+    std::vector<int64_t> shard;
+    for (int64_t i = 1; i < total; i += 2) shard.push_back(i);
+    ld.start_epoch(order, 100);
+    consume(ld, order, batch, rec_bytes, 1);
+    ld.start_epoch(shard, 101);
+    CHECK(consume(ld, shard, batch, rec_bytes, -1) == (int64_t)shard.size());
+    ld.start_epoch(order, 102);  // destroyed with workers busy
+  }
+  {
+    LoaderConfig c2 = cfg;
+    c2.drop_last = true;
+    RecordLoader ld(c2);
+    std::vector<int64_t> order(total);
+    std::iota(order.begin(), order.end(), 0);
+    ld.start_epoch(order, 0);
+    CHECK(ld.batches_per_epoch() == total / batch);
+    CHECK(consume(ld, order, batch, rec_bytes, -1) == (total / batch) * batch);
+  }
+  for (auto& f : cfg.files) unlink(f.c_str());
+  std::printf(g_fail ? "loader_raw_stress: %d check(s) FAILED\n" : "loader_raw_stress: ok\n", g_fail);
+  return g_fail ? 1 : 0;
+}
