@@ -2226,6 +2226,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("out") = py::none());
   m.def("set_splitk_target", [](int v) { mipipe::g_splitk_target = std::max(1, v); });
   m.def("get_splitk_target", []() { return mipipe::g_splitk_target; });
+  m.def("set_wgrad_xcd", [](bool on) { mipipe::g_wgrad_xcd = on ? 1 : 0; });
+  m.def("get_wgrad_xcd", []() { return mipipe::g_wgrad_xcd != 0; });
   m.def("set_stat_rows", [](int v) {
     TORCH_CHECK(v >= 1 && v <= mipipe::kStatReplicas, "stat rows must be in [1, ", mipipe::kStatReplicas, "]");
     mipipe::g_stat_rows = v;

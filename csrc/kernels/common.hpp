@@ -5,6 +5,8 @@
 #include <type_traits>
 #include <algorithm>
 
+#include "block_map.hpp"  // xcd_remap, splitk_block_map (host + device)
+
 namespace mipipe {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -207,14 +209,17 @@ struct FastDiv {
 
 __device__ __forceinline__ uint32_t fdiv(const FastDiv& f, uint32_t n) { return f.div(n); }
 
-// XCD-aware bijective remap of a linear workgroup id (guide §5 "XCD swizzle must be
-// bijective"): consecutive logical tiles land on the same XCD (shared L2).
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t wg, uint32_t nwg) {
-  constexpr uint32_t NX = 8;
-  if (nwg < NX) return wg;
-  uint32_t q = nwg / NX, r = nwg % NX;
-  uint32_t x = wg % NX, l = wg / NX;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + l;
+// (tile, split) of a split-K block and the launch's split count.  xcd_splits == 0: the launch is
+// grid(tiles, splits) — blockIdx.y is the split and the XCD remap runs over the tile axis only
+// (an XCD then holds every k-slice of a few tiles); xcd_splits > 0: a 1-D grid of
+// tiles * xcd_splits blocks placed by splitk_block_map (an XCD holds whole k-slices).
+struct SplitPos {
+  uint32_t tile, split, nsplit;
+};
+__device__ __forceinline__ SplitPos splitk_pos(uint32_t xcd_splits) {
+  if (xcd_splits == 0) return SplitPos{xcd_remap(blockIdx.x, gridDim.x), blockIdx.y, gridDim.y};
+  const TileSplit m = splitk_block_map(blockIdx.x, gridDim.x / xcd_splits, xcd_splits);
+  return SplitPos{m.tile, m.split, xcd_splits};
 }
 
 }  // namespace mipipe

@@ -374,14 +374,15 @@ __global__ __launch_bounds__(C::THREADS, (conv_occ<T, C>())) void conv_wgrad_ker
   __shared__ __attribute__((aligned(16))) char smem[lds_bytes_f32out<T, C>()];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  const uint32_t id = xcd_remap(blockIdx.x, gridDim.x);
-  const uint32_t tm = id / tilesN, tn = id % tilesN;
+  const SplitPos pos = splitk_pos(e.xcd_splits);
+  const uint32_t tm = pos.tile / tilesN, tn = pos.tile % tilesN;
   const uint32_t m0 = tm * BM, n0 = tn * BN;
   const uint32_t Co = e.M;
   const uint32_t K = (uint32_t)(g.N * g.Ho * g.Wo);
   const int nk = (int)((K + BK - 1) / BK);
-  const int kt0 = blockIdx.y * kt_per_split;
+  const int kt0 = pos.split * kt_per_split;
   const int kt1 = min(nk, kt0 + kt_per_split);
+  // once per launch: linear block 0 of either grid form
   if (e.col.rep != nullptr && blockIdx.x == 0 && blockIdx.y == 0) bn_collect_block<C::THREADS>(e.col);
   auto ia = [&](auto& a, uint32_t origin) { a.init(dy, Co, Co, K, origin, wave, lane, g_conv_zero); };
   auto ib = [&](auto& b, uint32_t origin) {

@@ -76,8 +76,13 @@ static void conv_wgrad_t(const void* dy, const void* x, float* dw, const ConvSha
     int splits, per;
     wgrad_grid<C>(s, tN, tiles, splits, per, splits_req);
     splits_used = splits;
-    const dim3 grid(tiles, splits), block(C::THREADS);
+    dim3 grid(tiles, splits);
+    const dim3 block(C::THREADS);
     EpiParams ee = e;
+    if (g_wgrad_xcd && splits > 1) {  // a k-slice's tiles on one XCD (splitk_block_map)
+      grid = dim3(tiles * splits);
+      ee.xcd_splits = splits;
+    }
     // unsplit (and not the deterministic workspace path): the block owns its output tile ->
     // non-atomic read-modify-write; the ATOMIC template also carries the workspace-slice store
     const bool atomic = splits > 1 || ws != nullptr;

@@ -42,7 +42,8 @@ struct EpiParams {
   // deterministic mode (det_rows > 0): no float atomics.  Statistics partials (st_sum / st_sq,
   // bnr_rep) are WRITTEN at row det_row0 + (m0 / BM) of [det_rows][N] slabs (bnr_rep: two
   // arrays det_rows apart) and summed in a fixed order afterwards (det.hip); split-K fp32
-  // outputs (epilogue_f32) are written to slice blockIdx.y of a [splits][M][ldc] workspace.
+  // outputs (epilogue_f32) are written to the block's split's slice (splitk_pos) of a
+  // [splits][M][ldc] workspace.
   int det_rows;
   int det_row0;
   // epilogue_f32 without ATOMIC: add the tile to the existing C (read-modify-write; each
@@ -52,6 +53,9 @@ struct EpiParams {
   BnCollect col;
   // workspace split-K finished by the last-arriving split (det_rows path; launchers.hpp)
   WsFinish fin;
+  // split-K weight-grads / GEMMs: > 0 = the launch is a 1-D grid of tiles * xcd_splits blocks
+  // placed by splitk_block_map (a k-slice's tiles share an XCD); 0 = grid(tiles, splits)
+  int xcd_splits;
   // non-temporal (streaming) stores of the output tile; streaming loads of the fused
   // data-grad epilogue's operand ring (addend / y / z)
   int nt, ntl;
@@ -142,20 +146,21 @@ __device__ void flip_block(const EpiParams& e, uint32_t b, char* smem) {
 // output.  Release: each split fences its slice stores (agent scope) before taking its ticket;
 // acquire: the last one fences again before reading the other splits' slices.
 template <int BM, int BN, int kThreads>
-__device__ void ws_finish(char* smem, const EpiParams& e, uint32_t m0, uint32_t n0) {
+__device__ void ws_finish(char* smem, const EpiParams& e, uint32_t m0, uint32_t n0,
+                          const SplitPos pos) {
   // release only (L2 write-back, no invalidate): a full __threadfence() also invalidates the
   // XCD's L2 in every block
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   __syncthreads();
   int* flag = reinterpret_cast<int*>(smem);
   if (threadIdx.x == 0) {
-    const int old = atomicAdd(e.fin.ticket + blockIdx.x, 1);
-    *flag = old == (int)gridDim.y - 1 ? 1 : 0;
+    const int old = atomicAdd(e.fin.ticket + pos.tile, 1);
+    *flag = old == (int)pos.nsplit - 1 ? 1 : 0;
   }
   __syncthreads();
   if (*flag == 0) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the last split only
-  const int S = (int)gridDim.y;
+  const int S = (int)pos.nsplit;
   const float* ws = reinterpret_cast<const float*>(e.C);
   const long slice = (long)e.M * e.ldc;
   constexpr int CPR = BN / 4;  // float4 chunks per tile row
@@ -189,7 +194,7 @@ __device__ void ws_finish(char* smem, const EpiParams& e, uint32_t m0, uint32_t 
           make_uint2(pack2(f[0], f[1]), pack2(f[2], f[3]));
     }
   }
-  if (threadIdx.x == 0) atomicExch(e.fin.ticket + blockIdx.x, 0);  // ready for the next launch
+  if (threadIdx.x == 0) atomicExch(e.fin.ticket + pos.tile, 0);  // ready for the next launch
 }
 
 // BnCollect riding in a kernel: the block sums the replica rows of a bwd slab that the previous
@@ -785,7 +790,11 @@ __device__ void epilogue_f32(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
   // stage fp32 tile: pitch BN*4 + 16 bytes (RP*(BN*4+16) <= LDS of the kernel)
   constexpr int P = BN * 4 + 16;
   float* C = reinterpret_cast<float*>(e.C);
-  if (ATOMIC && e.det_rows > 0) C += (long)blockIdx.y * e.M * e.ldc;
+  SplitPos pos{};
+  if (ATOMIC && e.det_rows > 0) {
+    pos = splitk_pos(e.xcd_splits);
+    C += (long)pos.split * e.M * e.ldc;
+  }
 #pragma unroll
   for (int pass = 0; pass < PASSES; ++pass) {
     if (pass > 0) __syncthreads();  // the previous pass's staging reads are done
@@ -861,7 +870,7 @@ __device__ void epilogue_f32(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
   if constexpr (ATOMIC) {
     if (e.det_rows > 0 && e.fin.ticket != nullptr) {
       __syncthreads();  // the staging reads of the last pass are done (ws_finish reuses smem)
-      ws_finish<BM, BN, kThreads>(smem, e, m0, n0);
+      ws_finish<BM, BN, kThreads>(smem, e, m0, n0, pos);
     }
   }
 }

@@ -13,6 +13,13 @@
 
 namespace mipipe {
 int g_splitk_target = 512;
+// Split-K block placement (weight-grads, split-K GEMMs): 1 = 1-D grid placed by splitk_block_map,
+// every tile of a k-slice on one XCD; 0 = grid(tiles, splits), the XCD remap over the tile axis
+// only (MIPIPE_WGRAD_XCD overrides; A/B in profiles/wgrad_xcd_after.txt)
+int g_wgrad_xcd = [] {
+  const char* v = getenv("MIPIPE_WGRAD_XCD");
+  return v != nullptr ? (atoi(v) != 0 ? 1 : 0) : 1;
+}();
 int g_ns1_max_k_gather = 1152;  // measured: tools/sweep_ns1_gather.py (profiles/r1_ns1_gather_sweep.jsonl)
 int g_stat_rows = kStatReplicas;
 // Non-temporal (streaming) stores of large activation outputs, a bit mask: 1 conv forward,
@@ -68,15 +75,16 @@ __global__ __launch_bounds__(C::THREADS, (conv_occ<T, C>())) void gemm_dense_ker
   __shared__ __attribute__((aligned(16))) char smem[main_lds > epi_lds ? main_lds : epi_lds];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  const uint32_t id = xcd_remap(blockIdx.x, gridDim.x);
-  const uint32_t tm = id / tilesN, tn = id % tilesN;
+  const SplitPos pos = splitk_pos(e.xcd_splits);
+  const uint32_t tm = pos.tile / tilesN, tn = pos.tile % tilesN;
   const uint32_t m0 = tm * BM, n0 = tn * BN;
   const int nk = (int)((K + BK - 1) / BK);
-  const int kt0 = blockIdx.y * kt_per_split;
+  const int kt0 = pos.split * kt_per_split;
   const int kt1 = min(nk, kt0 + kt_per_split);
   auto ia = [&](auto& a, uint32_t origin) { a.init(A, lda, e.M, K, origin, wave, lane, g_gemm_zero); };
   auto ib = [&](auto& b, uint32_t origin) { b.init(B, ldb, e.N, K, origin, wave, lane, g_gemm_zero); };
   // cache warming for the next GEMM (e.pf_*): issued first, so the loads overlap the main loop
+  // (the linear block id of either grid form: a 1-D split-K grid has gridDim.y == 1)
   const uint32_t pf_acc =
       pf_issue<C::THREADS>(e, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
   f32x4 acc[BM / C::WM / 16][BN / C::WN / 16];
@@ -98,9 +106,13 @@ static inline uint32_t cdiv_u(uint64_t a, uint64_t b) { return (uint32_t)((a + b
 
 template <class C, bool AK, bool BK_, class T>
 static void launch_out(const void* A, long lda, const void* B, long ldb, int K, uint32_t tN,
-                       uint32_t tiles, int splits, int per, int out, const EpiParams& e,
+                       uint32_t tiles, int splits, int per, int out, EpiParams e,
                        hipStream_t st) {
   dim3 grid(tiles, splits);
+  if (g_wgrad_xcd && splits > 1) {  // split-K: a k-slice's tiles on one XCD (splitk_block_map)
+    grid = dim3(tiles * splits);
+    e.xcd_splits = splits;
+  }
   const T* a = (const T*)A;
   const T* b = (const T*)B;
   // a 256 x 256 fp32 tile does not fit the LDS: the 2-phase loop's 256 x 256 tile only serves

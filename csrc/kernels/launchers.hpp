@@ -30,6 +30,9 @@ extern int g_stat_rows;
 // Split-K sizing for the atomically-accumulated weight-gradient GEMMs: splits are chosen so
 // that tiles * splits ~= this many workgroups (tunable at runtime for sweeps).
 extern int g_splitk_target;
+// Split-K launches (conv weight-grads, wgrad3x3, split-K GEMMs) as a 1-D grid whose blocks
+// splitk_block_map (block_map.hpp) places so that the tiles of one k-slice share an XCD's L2.
+extern int g_wgrad_xcd;
 // Dense (1x1) conv fwd/dgrad with reduction K <= this use the single-LDS-stage kernels.
 extern int g_ns1_max_k;
 extern int g_ns1_max_k_gather;  // same for the gathered (im2col / strided dgrad) convs

@@ -4,7 +4,8 @@
 //
 // The generic weight-grad (conv_wgrad.hip) is an implicit GEMM whose B operand is im2col(x):
 // every input element is fetched once per filter tap (9x through L2) and every block re-reads
-// dy for each of its N tiles.  Here a k-step is a group of R consecutive output rows of ONE
+// dy for each of its N tiles (from its XCD's L2 once the k-slice's tiles share one: the split-K
+// block placement, block_map.hpp).  Here a k-step is a group of R consecutive output rows of ONE
 // image (R*W <= 64 pixels, padded to 64 MFMA k-slots); the block stages
 //   * the dy rows   [64 slots][64 co]                (8 KB, the A operand), and
 //   * the x patch   [(R+2) rows][(W+2) cols][64 ci]  (<= 24 KB, zero halo)
@@ -17,7 +18,10 @@
 // Block = 64 co x 64 ci x 9 taps (4 waves; wave w owns ci [16w, 16w+16) for all 64 co and 9 taps:
 // 36 accumulators, A fragments shared by the 9 taps).  The reduction over pixels is split over
 // S blocks per tile; each writes its fp32 partial tile to a workspace slice and a fixed-order
-// sum adds the slices into dW (det.hip splitk_sum) — deterministic in both modes.
+// sum adds the slices into dW (det.hip splitk_sum) — deterministic in both modes.  The tiles x S
+// blocks are a 1-D grid placed by splitk_block_map (g_wgrad_xcd): the tiles of one k-slice, which
+// share dy across ci tiles and x across co tiles, run on one XCD.  Measured: L2 fills drop 3x
+// (profiles/wgrad_xcd_after.txt) but the time does not move — this kernel is not fill-bound.
 #include <cstdlib>
 #include <utility>
 
@@ -125,7 +129,7 @@ __device__ __forceinline__ void units(Frags<CB>& f, f32x4 (&acc)[9][CB], FB& iss
 template <int NW>
 __global__ __launch_bounds__(64 * NW, NW / 4) void wgrad3x3_kernel(
     const __bf16* __restrict__ dy, const __bf16* __restrict__ x, float* __restrict__ ws, Geo g,
-    BnCollect col) {
+    BnCollect col, int xcd_splits) {
   constexpr int CB = 16 / NW;                  // co blocks (16 co) per wave
   constexpr int DYI = 8 / NW;                  // dy-image glds per wave per stage
   constexpr int PTI = kPatchPix / (NW * 8);    // patch glds per wave per stage
@@ -143,9 +147,16 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void wgrad3x3_kernel(
   const int lane = threadIdx.x & 63;
   if (col.rep != nullptr && blockIdx.x == 0 && blockIdx.y == 0) gk::bn_collect_block<64 * NW>(col);
   const int tilesC = g.Ci / TC;
-  const int tile = blockIdx.x;
+  // xcd_splits > 0: 1-D grid, a k-slice's tiles (which share dy across ci tiles and x across co
+  // tiles) placed on one XCD; else grid(tiles, splits)
+  int tile = blockIdx.x, split = blockIdx.y;
+  if (xcd_splits > 0) {
+    const TileSplit m = splitk_block_map(blockIdx.x, gridDim.x / xcd_splits, xcd_splits);
+    tile = (int)m.tile;
+    split = (int)m.split;
+  }
   const int co0 = (tile / tilesC) * TM, ci0 = (tile % tilesC) * TC;
-  const int s0 = blockIdx.y * g.per;
+  const int s0 = split * g.per;
   const int s1 = min(g.steps, s0 + g.per);
   const int W = g.W, H = g.H, PW = g.PW, RW = g.R * g.W;
   const __bf16* zero = reinterpret_cast<const __bf16*>(gk::g_conv_zero);
@@ -271,8 +282,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void wgrad3x3_kernel(
     }
     wait_vmcnt<0>();  // the trailing dummy stages
   }
-  // ---- partial tile -> workspace slice blockIdx.y: lane holds C[co][ci..ci+3] per (tap, i)
-  float* out = ws + (long)blockIdx.y * g.ws_stride;
+  // ---- partial tile -> this split's workspace slice: lane holds C[co][ci..ci+3] per (tap, i)
+  float* out = ws + (long)split * g.ws_stride;
   const int ci = ci0 + wci * 16 + 4 * (lane >> 4);
 #pragma unroll
   for (int t = 0; t < 9; ++t)
@@ -331,12 +342,14 @@ void conv_wgrad3x3(const void* dy, const void* x, float* dw, const ConvShape& s,
   const int tiles = (s.Co / w3::TM) * (s.Ci / w3::TC);
   BnCollect c{};
   if (col != nullptr) c = *col;
+  const int xs = g_wgrad_xcd && S > 1 ? S : 0;
+  const dim3 grid = xs > 0 ? dim3(tiles * S) : dim3(tiles, S);
   if (g_wgrad3x3_waves == 4)
-    hipLaunchKernelGGL(w3::wgrad3x3_kernel<4>, dim3(tiles, S), dim3(256), 0, st,
-                       (const __bf16*)dy, (const __bf16*)x, ws, g, c);
+    hipLaunchKernelGGL(w3::wgrad3x3_kernel<4>, grid, dim3(256), 0, st,
+                       (const __bf16*)dy, (const __bf16*)x, ws, g, c, xs);
   else
-    hipLaunchKernelGGL(w3::wgrad3x3_kernel<8>, dim3(tiles, S), dim3(512), 0, st,
-                       (const __bf16*)dy, (const __bf16*)x, ws, g, c);
+    hipLaunchKernelGGL(w3::wgrad3x3_kernel<8>, grid, dim3(512), 0, st,
+                       (const __bf16*)dy, (const __bf16*)x, ws, g, c, xs);
   splitk_sum(ws, S, g.ws_stride, dw, st);
 }
 
