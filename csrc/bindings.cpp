@@ -1511,6 +1511,46 @@ std::tuple<Tensor, Tensor> record_decode(Tensor rec, Tensor idx, Tensor affine, 
   return {x, y};
 }
 
+// The loader's "rrc" transform on the device (RandomResizedCrop / centre crop + bilinear resize
+// + flip + normalise): same inputs as record_decode, x is [n, C, Ho, Wo].
+std::tuple<Tensor, Tensor> record_decode_rrc(Tensor rec, Tensor idx, Tensor affine, int64_t C,
+                                             int64_t H, int64_t W, int64_t Ho, int64_t Wo,
+                                             uint64_t seed, int64_t epoch, bool flip, bool train,
+                                             int64_t label_bytes, at::ScalarType dtype) {
+  check_cuda(rec, "rec");
+  check_cuda(idx, "idx");
+  check_f32(affine, "affine");
+  c10::DeviceGuard g(rec.device());
+  TORCH_CHECK(rec.scalar_type() == at::kByte, "rec must be uint8, got ", rec.scalar_type());
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64, got ", idx.scalar_type());
+  TORCH_CHECK(idx.device() == rec.device() && affine.device() == rec.device(),
+              "rec, idx and affine must be on one device");
+  const bool bf = dtype == at::kBFloat16;
+  TORCH_CHECK(bf || dtype == at::kFloat, "record_decode_rrc produces fp32 or bf16");
+  TORCH_CHECK(C >= 1 && H >= 2 && W >= 2 && H <= 32768 && W <= 32768 &&
+                  C * H * W < (1ll << 31), "bad stored shape (H, W in [2, 32768])");
+  TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho + Wo <= mipipe::record_decode_rrc_max_extent_sum &&
+                  C * Ho * Wo < (1ll << 31),
+              "bad output size ", Ho, "x", Wo, " (positive, Ho + Wo <= ",
+              mipipe::record_decode_rrc_max_extent_sum, ")");
+  TORCH_CHECK(label_bytes >= 1 && label_bytes <= 8, "label_bytes must be in [1, 8]");
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == label_bytes + C * H * W, "rec must be [n, ",
+              label_bytes + C * H * W, "] (label bytes + C*H*W)");
+  TORCH_CHECK(rec.is_contiguous() && idx.is_contiguous(), "rec and idx must be contiguous");
+  const int64_t n = rec.size(0);
+  TORCH_CHECK(idx.dim() == 1 && idx.size(0) == n, "idx must be [n]");
+  TORCH_CHECK(affine.dim() == 2 && affine.size(0) == 2 && affine.size(1) == C,
+              "affine must be [2, C]");
+  auto x = torch::empty({n, C, Ho, Wo}, rec.options().dtype(dtype));
+  auto y = torch::empty({n}, rec.options().dtype(at::kLong));
+  if (n == 0) return {x, y};
+  mipipe::record_decode_rrc(rec.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(),
+                            affine.data_ptr<float>(), x.data_ptr(), bf, y.data_ptr<int64_t>(), n,
+                            (int)C, (int)H, (int)W, (int)Ho, (int)Wo, (int)label_bytes, seed,
+                            (uint64_t)epoch, flip, train, stream());
+  return {x, y};
+}
+
 // ------------------------------------------------------------------------------- transformer ops
 Tensor gelu_fwd(Tensor x) {
   check_bf16(x, "x");
@@ -2191,6 +2231,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("C"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("epoch"),
         py::arg("pad"), py::arg("flip"), py::arg("train"), py::arg("label_bytes"),
         py::arg("dtype"));
+  m.def("record_decode_rrc", &record_decode_rrc, py::arg("rec"), py::arg("idx"),
+        py::arg("affine"), py::arg("C"), py::arg("H"), py::arg("W"), py::arg("Ho"), py::arg("Wo"),
+        py::arg("seed"), py::arg("epoch"), py::arg("flip"), py::arg("train"),
+        py::arg("label_bytes"), py::arg("dtype"));
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
   m.def("gemm_gelu", &gemm_gelu, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(),

@@ -389,6 +389,15 @@ void synthetic_batch(const int64_t* idx, int n, int C, int H, int W, int classes
 void record_decode(const uint8_t* rec, const int64_t* idx, const float* affine, void* x,
                    bool bf16_out, int64_t* y, long n, int C, int H, int W, int label_bytes,
                    uint64_t seed, uint64_t epoch, int pad, bool flip, bool train, hipStream_t st);
+// The "rrc" transform on the same records: x [n][C][Ho][Wo] is the box of mipipe_rrc::rrc_box
+// (common/rrc.hpp: RandomResizedCrop in training, 7/8 centre crop otherwise) resampled
+// bilinearly, flipped and normalised — RecordLoader::fill_rrc bit for bit.  H, W in [2, 32768],
+// (Ho + Wo) * 8 bytes of LDS tap tables: Ho + Wo <= record_decode_rrc_max_extent_sum.
+constexpr int record_decode_rrc_max_extent_sum = 8000;
+void record_decode_rrc(const uint8_t* rec, const int64_t* idx, const float* affine, void* x,
+                       bool bf16_out, int64_t* y, long n, int C, int H, int W, int Ho, int Wo,
+                       int label_bytes, uint64_t seed, uint64_t epoch, bool flip, bool train,
+                       hipStream_t st);
 // Fused ResNet stem on the packed input (stem.hip): conv 7x7/2 (packed K = 224, 64 channels,
 // 112 output columns) -> BN -> ReLU -> max-pool 3x3/2/1.
 //   stem_fwd_stats : shifted Σ, Σ² of bf16(y) per channel (conv recomputed, y not stored) ->

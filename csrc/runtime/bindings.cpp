@@ -2,6 +2,9 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <stdexcept>
+
+#include "../common/rrc.hpp"
 #include "runtime.hpp"
 
 namespace py = pybind11;
@@ -59,7 +62,26 @@ PYBIND11_MODULE(_runtime, m) {
       .def_readwrite("workers", &LoaderConfig::workers)
       .def_readwrite("prefetch", &LoaderConfig::prefetch)
       .def_readwrite("drop_last", &LoaderConfig::drop_last)
-      .def_readwrite("raw", &LoaderConfig::raw);
+      .def_readwrite("raw", &LoaderConfig::raw)
+      .def_readwrite("transform", &LoaderConfig::transform)
+      .def_readwrite("out_h", &LoaderConfig::out_h)
+      .def_readwrite("out_w", &LoaderConfig::out_w);
+
+  // the "rrc" transform's geometry (csrc/common/rrc.hpp), for tests against the Python definition
+  m.def("rrc_box",
+        [](uint64_t seed, uint64_t epoch, uint64_t index, int H, int W, bool train, bool flip) {
+          if (H < 2 || W < 2 || H > 32768 || W > 32768)
+            throw std::invalid_argument("rrc_box needs H, W in [2, 32768]");
+          const mipipe_rrc::Box b = mipipe_rrc::rrc_box(seed, epoch, index, H, W, train, flip);
+          return py::make_tuple(b.y0, b.x0, b.h, b.w, b.flip);
+        },
+        py::arg("seed"), py::arg("epoch"), py::arg("index"), py::arg("H"), py::arg("W"),
+        py::arg("train"), py::arg("flip") = true);
+  m.def("rrc_ratio_q16", [] {
+    std::vector<uint32_t> v(mipipe_rrc::kRatios);
+    for (int t = 0; t < mipipe_rrc::kRatios; ++t) v[t] = mipipe_rrc::ratio_q16(t);
+    return v;
+  });
 
   py::class_<RecordLoader>(m, "RecordLoader")
       .def(py::init<const LoaderConfig&>())

@@ -11,7 +11,11 @@
 // re-sharded run sees the same crops/flips for the same sample and epoch.
 // Raw mode (LoaderConfig::raw): the workers only gather — whole records and their global sample
 // indices go through the same ring, and the transform runs on the GPU (csrc/kernels/records.hip).
+// LoaderConfig::transform "rrc": RandomResizedCrop + flip + Normalize to out_h x out_w instead of
+// the same-size crop (fill_rrc; geometry in csrc/common/rrc.hpp, shared with the device kernel).
 #include "runtime.hpp"
+
+#include "../common/rrc.hpp"
 
 #include <fcntl.h>
 #include <string.h>
@@ -36,6 +40,20 @@ RecordLoader::RecordLoader(const LoaderConfig& cfg) : cfg_(cfg) {
     throw std::invalid_argument("bad loader geometry");
   if ((int)cfg_.mean.size() != cfg_.C || (int)cfg_.stdv.size() != cfg_.C)
     throw std::invalid_argument("mean/std must have C entries");
+  if (cfg_.transform != "crop" && cfg_.transform != "rrc")
+    throw std::invalid_argument("transform must be \"crop\" or \"rrc\"");
+  rrc_ = cfg_.transform == "rrc";
+  if (rrc_) {
+    if (cfg_.out_h == 0) cfg_.out_h = cfg_.H;
+    if (cfg_.out_w == 0) cfg_.out_w = cfg_.W;
+    const int lim = 32768;  // rrc.hpp's products stay inside 64 bits
+    if (std::min(cfg_.H, cfg_.W) < 2 || cfg_.out_h < 1 || cfg_.out_w < 1 ||
+        std::max(std::max(cfg_.H, cfg_.W), std::max(cfg_.out_h, cfg_.out_w)) > lim)
+      throw std::invalid_argument("rrc needs stored extents in [2, 32768] and output extents in [1, 32768]");
+  } else if ((cfg_.out_h && cfg_.out_h != cfg_.H) || (cfg_.out_w && cfg_.out_w != cfg_.W)) {
+    throw std::invalid_argument("out_h / out_w need transform \"rrc\"");
+  }
+  out_per_ = rrc_ ? (size_t)cfg_.C * cfg_.out_h * cfg_.out_w : (size_t)cfg_.C * cfg_.H * cfg_.W;
   rec_bytes_ = (size_t)cfg_.label_bytes + (size_t)cfg_.C * cfg_.H * cfg_.W;
   for (auto& f : cfg_.files) {
     int fd = open(f.c_str(), O_RDONLY | O_CLOEXEC);
@@ -61,10 +79,9 @@ RecordLoader::RecordLoader(const LoaderConfig& cfg) : cfg_(cfg) {
   slot_raw_.resize(cfg_.prefetch);
   slot_n_.assign(cfg_.prefetch, 0);
   slot_batch_.assign(cfg_.prefetch, -1);
-  const size_t per = (size_t)cfg_.C * cfg_.H * cfg_.W;
   for (int s = 0; s < cfg_.prefetch; ++s) {
     if (cfg_.raw) slot_raw_[s].resize((size_t)cfg_.batch * rec_bytes_);  // no float slots
-    else slot_x_[s].resize((size_t)cfg_.batch * per);
+    else slot_x_[s].resize((size_t)cfg_.batch * out_per_);
     slot_y_[s].resize(cfg_.batch);
   }
   for (int w = 0; w < std::max(1, cfg_.workers); ++w) threads_.emplace_back([this] { worker(); });
@@ -150,6 +167,60 @@ void RecordLoader::fill(int slot, int64_t b, const std::vector<int64_t>& idx, in
   slot_n_[slot] = n;
 }
 
+// "rrc": the box of rrc_box() resampled bilinearly to out_h x out_w, flipped, normalised.  The
+// horizontal blend (8-bit pixels, Q16 weights) is exact in fp32; the vertical one is two rounded
+// multiplies and a rounded add, then v * sc + off as in fill() — the NumPy definition
+// (records.py reference_transform_rrc) and records.hip produce the same bits.
+void RecordLoader::fill_rrc(int slot, int64_t b, const std::vector<int64_t>& idx, int64_t epoch) {
+  namespace rrc = mipipe_rrc;
+  const int C = cfg_.C, H = cfg_.H, W = cfg_.W, Ho = cfg_.out_h, Wo = cfg_.out_w;
+  const int64_t i0 = b * cfg_.batch;
+  const int n = (int)std::min<int64_t>(cfg_.batch, (int64_t)idx.size() - i0);
+  float* xo = slot_x_[slot].data();
+  int64_t* yo = slot_y_[slot].data();
+  const size_t plane = (size_t)H * W, oplane = (size_t)Ho * Wo;
+  // the column taps of one sample, the flip folded in: source columns and their weights
+  std::vector<int> cx0(Wo), cx1(Wo);
+  std::vector<float> lx0(Wo), lx1(Wo);
+  for (int s = 0; s < n; ++s) {
+    const int64_t gi = idx[i0 + s];
+    const uint8_t* r = record(gi);
+    int64_t label = 0;
+    for (int k = 0; k < cfg_.label_bytes; ++k) label |= (int64_t)r[k] << (8 * k);
+    yo[s] = label;
+    const uint8_t* img = r + cfg_.label_bytes;
+    const rrc::Box bx = rrc::rrc_box(cfg_.seed, (uint64_t)epoch, (uint64_t)gi, H, W, cfg_.train,
+                                     cfg_.flip);
+    for (int x = 0; x < Wo; ++x) {
+      const rrc::Tap t = rrc::rrc_tap(bx.flip ? Wo - 1 - x : x, bx.w, Wo);
+      cx0[x] = bx.x0 + t.i0;
+      cx1[x] = bx.x0 + t.i1;
+      lx1[x] = (float)t.frac * (1.f / 65536.f);
+      lx0[x] = 1.f - lx1[x];
+    }
+    float* xs = xo + (size_t)s * C * oplane;
+    for (int y = 0; y < Ho; ++y) {
+      const rrc::Tap t = rrc::rrc_tap(y, bx.h, Ho);
+      const float ly1 = (float)t.frac * (1.f / 65536.f), ly0 = 1.f - ly1;
+      for (int c = 0; c < C; ++c) {
+        const float sc = 1.f / (255.f * cfg_.stdv[c]);
+        const float off = -cfg_.mean[c] / cfg_.stdv[c];
+        const uint8_t* r0 = img + (size_t)c * plane + (size_t)(bx.y0 + t.i0) * W;
+        const uint8_t* r1 = img + (size_t)c * plane + (size_t)(bx.y0 + t.i1) * W;
+        float* op = xs + (size_t)c * oplane + (size_t)y * Wo;
+        for (int x = 0; x < Wo; ++x) {
+          const float top = (float)r0[cx0[x]] * lx0[x] + (float)r0[cx1[x]] * lx1[x];
+          const float bot = (float)r1[cx0[x]] * lx0[x] + (float)r1[cx1[x]] * lx1[x];
+          const float ta = top * ly0, tb = bot * ly1;
+          const float v = ta + tb;
+          op[x] = v * sc + off;
+        }
+      }
+    }
+  }
+  slot_n_[slot] = n;
+}
+
 // raw mode: gather only — whole records (label bytes included) and their global indices
 void RecordLoader::fill_raw(int slot, int64_t b, const std::vector<int64_t>& idx) {
   const int64_t i0 = b * cfg_.batch;
@@ -179,6 +250,7 @@ void RecordLoader::worker() {
     ++busy_;
     g.unlock();
     if (cfg_.raw) fill_raw(slot, b, *idx);
+    else if (rrc_) fill_rrc(slot, b, *idx, epoch);
     else fill(slot, b, *idx, epoch);
     g.lock();
     --busy_;
@@ -197,8 +269,7 @@ int RecordLoader::next(float* x, int64_t* y) {
   if (shutdown_) return 0;
   const int n = slot_n_[slot];
   g.unlock();
-  const size_t per = (size_t)cfg_.C * cfg_.H * cfg_.W;
-  memcpy(x, slot_x_[slot].data(), (size_t)n * per * sizeof(float));
+  memcpy(x, slot_x_[slot].data(), (size_t)n * out_per_ * sizeof(float));
   memcpy(y, slot_y_[slot].data(), (size_t)n * sizeof(int64_t));
   g.lock();
   slot_batch_[slot] = -1;

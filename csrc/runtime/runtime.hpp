@@ -99,6 +99,11 @@ struct LoaderConfig {
   // raw mode: workers only gather whole records (label bytes included) and their global sample
   // indices; crop / flip / normalise run on the device (csrc/kernels/records.hip)
   bool raw = false;
+  // "crop": RandomCrop(pad) + flip + Normalize at the stored size.  "rrc": RandomResizedCrop +
+  // flip + Normalize (train) / 7/8 centre crop (eval), resized bilinearly to out_h x out_w
+  // (0 = stored size); the geometry is csrc/common/rrc.hpp, pad is not used.
+  std::string transform = "crop";
+  int out_h = 0, out_w = 0;
 };
 
 class RecordLoader {
@@ -107,7 +112,8 @@ class RecordLoader {
   ~RecordLoader();
   int64_t size() const { return total_; }
   void start_epoch(const std::vector<int64_t>& indices, int64_t epoch);
-  // copies the next batch to x [n,C,H,W] f32 / y [n] i64; returns n (0 = epoch exhausted)
+  // copies the next batch to x [n,C,H,W] f32 ("rrc": [n,C,out_h,out_w]) / y [n] i64; returns n
+  // (0 = epoch exhausted)
   int next(float* x, int64_t* y);
   // raw mode: copies the next batch's records to rec [n, record_bytes] u8 and their global sample
   // indices to idx [n] i64; returns n (0 = epoch exhausted)
@@ -119,9 +125,12 @@ class RecordLoader {
  private:
   void worker();
   void fill(int slot, int64_t b, const std::vector<int64_t>& idx, int64_t epoch);
+  void fill_rrc(int slot, int64_t b, const std::vector<int64_t>& idx, int64_t epoch);
   void fill_raw(int slot, int64_t b, const std::vector<int64_t>& idx);
   LoaderConfig cfg_;
+  bool rrc_ = false;
   size_t rec_bytes_ = 0;
+  size_t out_per_ = 0;  // floats of one decoded sample
   std::vector<std::pair<const uint8_t*, size_t>> maps_;
   std::vector<int64_t> file_start_;
   int64_t total_ = 0;

@@ -5,7 +5,8 @@ pytorch-pipeline.ipynb:218-221); its notebook placeholders (nb:10, nb:20) ask fo
 before training.  This pipeline completes that design on one MI355X node:
 
 1. ``preprocess`` writes the dataset as CIFAR-binary record files (synthetic & learnable: no
-   network) into a ``Dataset`` artifact;
+   network) into a ``Dataset`` artifact, with a manifest (stored shape, label width, class count,
+   mean / std) that ``train`` and ``evaluate`` read;
 2. ``train`` launches the distributed training job through the aiplatform-compatible job API
    (local launcher, one rank per GPU, RCCL DDP) running mipipe's task.py on those records via
    the native multi-threaded loader; the trained model lands in a ``Model`` artifact;
@@ -16,6 +17,12 @@ before training.  This pipeline completes that design on one MI355X node:
 
 Run (8 GPUs, ResNet-50 @ CIFAR shape):
   python examples/three_step_pipeline.py --gpus 8 --arch resnet50 --epochs 2
+Run (8 GPUs, ResNet-50 @ ImageNet shape: 256x256 records, 1000 classes, 2-byte labels;
+RandomResizedCrop(224) + flip for training and the 7/8 centre crop for evaluation, both decoded
+on the GPU):
+  python examples/three_step_pipeline.py --gpus 8 --arch resnet50 --dataset imagenet \
+      --record-size 256 --image-size 224 --num-classes 1000 --epochs 2 \
+      --extra-args '["--device-decode=1"]'
 CPU smoke (config 1 style):
   python examples/three_step_pipeline.py --gpus 0 --arch mnist_cnn --dataset mnist --epochs 1
 """
@@ -33,11 +40,23 @@ from mipipe.dsl import (component, Input, Output, Dataset, Model, Metrics,  # no
 
 
 @component()
-def preprocess(dataset: str, n_train: int, n_test: int, seed: int, data: Output[Dataset]):
+def preprocess(dataset: str, n_train: int, n_test: int, seed: int, record_size: int,
+               num_classes: int, label_bytes: int, data: Output[Dataset]):
+    """``record_size`` (stored H = W), ``num_classes``, ``label_bytes``: 0 = the dataset's own
+    (10 classes; 2-byte labels from 257 classes on)."""
     import json
     import os
-    from mipipe.data.records import write_synthetic_dataset
-    man = write_synthetic_dataset(data.path, dataset, n_train=n_train, n_test=n_test, seed=seed)
+    from mipipe.data import records as REC
+    from mipipe.data.synthetic import DATASET_SHAPES
+    ncls = num_classes or 10
+    lb = label_bytes or (2 if ncls > 256 else 1)
+    shape = (DATASET_SHAPES[dataset][0], record_size, record_size) if record_size else None
+    man = REC.write_synthetic_dataset(data.path, dataset, n_train=n_train, n_test=n_test,
+                                      seed=seed, num_classes=ncls, shape=shape, label_bytes=lb)
+    mean, std = {"mnist": (REC.MNIST_MEAN, REC.MNIST_STD),
+                 "imagenet": (REC.IMAGENET_MEAN, REC.IMAGENET_STD)}.get(
+                     dataset, (REC.CIFAR10_MEAN, REC.CIFAR10_STD))
+    man.update(mean=list(mean), std=list(std))
     data.metadata.update({k: v for k, v in man.items() if k != "files"})
     with open(os.path.join(data.path, "manifest.json"), "w") as f:
         json.dump(man, f)
@@ -46,8 +65,8 @@ def preprocess(dataset: str, n_train: int, n_test: int, seed: int, data: Output[
 
 @component()
 def train(data: Input[Dataset], arch: str, dataset: str, epochs: int, batch_size: int,
-          gpus: int, learning_rate: float, extra_args: str, model: Output[Model],
-          metrics: Output[Metrics]) -> float:
+          gpus: int, learning_rate: float, extra_args: str, image_size: int,
+          model: Output[Model], metrics: Output[Metrics]) -> float:
     import json
     import os
     from datetime import datetime
@@ -61,7 +80,7 @@ def train(data: Input[Dataset], arch: str, dataset: str, epochs: int, batch_size
             f"--data-dir={data.path}", f"--num_epochs={epochs}", f"--batch_size={batch_size}",
             f"--learning_rate={learning_rate}", "--eval-every=1000", "--log-every=10",
             "--model_filename=model.pth", f"--num_classes={int(data.metadata.get('num_classes', 10))}"
-            ] + json.loads(extra_args)
+            ] + ([f"--image-size={image_size}"] if image_size else []) + json.loads(extra_args)
     if gpus > 1:
         args.append("--multiprocessing-distributed")
     job = aiplatform.CustomTrainingJob(display_name=f"train_{arch}_{ts}",
@@ -85,7 +104,8 @@ def train(data: Input[Dataset], arch: str, dataset: str, epochs: int, batch_size
                                     metrics.log_metric(k, v)
     if not found:
         raise RuntimeError("training job produced no metrics line")
-    model.metadata.update({"arch": arch, "dataset": dataset, "framework": "mipipe"})
+    model.metadata.update({"arch": arch, "dataset": dataset, "framework": "mipipe",
+                           "image_size": image_size})
     return acc * 100.0
 
 
@@ -96,8 +116,10 @@ def evaluate(data: Input[Dataset], model: Input[Model], arch: str, dataset: str,
                                                                      ("deploy", str)]):
     import os
     from collections import namedtuple
+    import json
     import torch
     from mipipe.data import records as REC
+    from mipipe.data.synthetic import DATASET_SHAPES
     from mipipe.models import create_model
     from mipipe.train.checkpoint import strip_module_prefix
 
@@ -108,19 +130,34 @@ def evaluate(data: Input[Dataset], model: Input[Model], arch: str, dataset: str,
                 path = os.path.join(root, fn)
     if path is None:
         raise FileNotFoundError(f"no model.pth under {model.path}")
-    shape = (3, 32, 32) if dataset == "cifar10" else (1, 28, 28)
+    # stored shape, label width and mean / std: the manifest preprocess wrote, else the metadata
+    man = dict(data.metadata)
+    mpath = os.path.join(data.path, "manifest.json")
+    if os.path.isfile(mpath):
+        with open(mpath) as f:
+            man.update(json.load(f))
+    shape = tuple(int(v) for v in man.get("shape", DATASET_SHAPES[dataset][:3]))
+    size = int(model.metadata.get("image_size", 0)) or DATASET_SHAPES[dataset][1]
     sd = strip_module_prefix(torch.load(path, map_location="cpu", weights_only=True))
     head = [v for k, v in sd.items() if v.dim() == 2][-1]  # classifier weight [classes, feat]
     ncls = int(head.shape[0])
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
-    net = create_model(arch, num_classes=ncls)
+    kw = ({"in_chans": shape[0]}
+          if arch == "mnist_cnn" or arch.startswith(("resnet", "wide_resnet", "resnext")) else {})
+    net = create_model(arch, num_classes=ncls, **kw)
     net.load_state_dict(sd)
     net = net.to(dev).eval()
     mean, std = ((REC.MNIST_MEAN, REC.MNIST_STD) if dataset == "mnist"
                  else (REC.CIFAR10_MEAN, REC.CIFAR10_STD))
+    if "mean" in man and "std" in man:
+        mean, std = tuple(man["mean"]), tuple(man["std"])
     files = REC.dataset_files(data.path, dataset, "test")
+    # stored size != model size: the rrc evaluation transform (7/8 centre crop, resized)
+    rkw = ({"transform": "rrc", "out_size": (size, size)} if shape[1:] != (size, size) else {})
     loader = REC.RecordDataLoader(files, shape, 256, train=False, mean=mean, std=std,
-                                  device=dev)
+                                  device=dev, label_bytes=int(man.get("label_bytes", 1)),
+                                  decode="device" if dev.type == "cuda" and rkw else "host",
+                                  **rkw)
     cm = torch.zeros(ncls, ncls, dtype=torch.int64, device=dev)
     with torch.no_grad():
         for x, y in loader:
@@ -153,10 +190,11 @@ def deploy(model: Input[Model], serving_dir: str) -> str:
 def pipeline(baseline_accuracy: float = 70.0, dataset: str = "cifar10", arch: str = "resnet50",
              n_train: int = 10000, n_test: int = 2000, epochs: int = 2, batch_size: int = 256,
              gpus: int = 8, learning_rate: float = 0.1, extra_args: str = "[]",
-             serving_dir: str = "/tmp/mipipe_serving", seed: int = 0):
-    pre = preprocess(dataset, n_train, n_test, seed)
+             serving_dir: str = "/tmp/mipipe_serving", seed: int = 0, record_size: int = 0,
+             image_size: int = 0, num_classes: int = 0, label_bytes: int = 0):
+    pre = preprocess(dataset, n_train, n_test, seed, record_size, num_classes, label_bytes)
     tr = train(pre.outputs["data"], arch, dataset, epochs, batch_size, gpus, learning_rate,
-               extra_args)
+               extra_args, image_size)
     ev = evaluate(pre.outputs["data"], tr.outputs["model"], arch, dataset, baseline_accuracy)
     with kfp.dsl.Condition(ev.outputs["deploy"] == "true"):
         deploy(tr.outputs["model"], serving_dir)
@@ -175,6 +213,13 @@ def main(argv=None):
     ap.add_argument("--baseline-accuracy", type=float, default=70.0)
     ap.add_argument("--extra-args", default="[]")
     ap.add_argument("--serving-dir", default="/tmp/mipipe_serving")
+    ap.add_argument("--record-size", type=int, default=0,
+                    help="stored H = W of the records (0: the dataset's own shape)")
+    ap.add_argument("--image-size", type=int, default=0,
+                    help="model input H = W (0: the dataset's own); differs from the stored "
+                         "size -> RandomResizedCrop / centre-crop records (the rrc transform)")
+    ap.add_argument("--num-classes", type=int, default=0,
+                    help="classes of the synthetic set (0: 10); above 256 the labels take 2 bytes")
     ap.add_argument("--spec", default="three_step.json")
     ap.add_argument("--pipeline-root", default="gs://mipipe/pipeline_root")
     a = ap.parse_args(argv)
@@ -188,7 +233,8 @@ def main(argv=None):
                           "arch": a.arch, "n_train": a.n_train, "n_test": a.n_test,
                           "epochs": a.epochs, "batch_size": a.batch_size, "gpus": a.gpus,
                           "learning_rate": a.lr, "extra_args": a.extra_args,
-                          "serving_dir": a.serving_dir}, sync=True)
+                          "serving_dir": a.serving_dir, "record_size": a.record_size,
+                          "image_size": a.image_size, "num_classes": a.num_classes}, sync=True)
     run = client.get_run(resp["runId"])
     print(json.dumps({"run": resp["runId"], "state": run["state"],
                       "tasks": {k: v.get("state") for k, v in run.get("tasks", {}).items()}}))

@@ -14,9 +14,15 @@ transform runs on the GPU (csrc/kernels/records.hip), bit-identical to the host 
 
 :func:`reference_transform` is the plain-NumPy definition of the per-sample transform the
 native loader implements (tests compare the two bit-for-bit).
+
+A second transform, ``transform="rrc"``, resizes: RandomResizedCrop + flip + Normalize in
+training and a 7/8 centre crop in evaluation, from the stored size to any ``out_size`` (256x256
+records -> 224x224 batches).  Its geometry is integer-only, so :func:`reference_transform_rrc`,
+the native loader and the device kernel give the same bits.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Iterator, List, Optional, Sequence, Tuple
 
@@ -26,13 +32,16 @@ import torch
 from mipipe.parallel.sampler import DistributedSampler
 
 __all__ = ["write_records", "read_records", "write_synthetic_dataset", "reference_transform",
-           "RecordDataLoader", "CIFAR10_MEAN", "CIFAR10_STD", "dataset_files"]
+           "reference_rrc_box", "reference_transform_rrc", "RATIO_Q16", "RecordDataLoader",
+           "CIFAR10_MEAN", "CIFAR10_STD", "IMAGENET_MEAN", "IMAGENET_STD", "dataset_files"]
 
 # task.py:249-251
 CIFAR10_MEAN = (0.4914, 0.4822, 0.4465)
 CIFAR10_STD = (0.2023, 0.1994, 0.2010)
 MNIST_MEAN = (0.1307,)
 MNIST_STD = (0.3081,)
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
 
 _MASK64 = (1 << 64) - 1
 
@@ -46,6 +55,12 @@ def _check_label_bytes(label_bytes: int) -> int:
 def write_records(path: str, images: np.ndarray, labels: np.ndarray, label_bytes: int = 1) -> None:
     """images uint8 [N, C, H, W], labels [N] (< 256 ** label_bytes, stored little-endian) ->
     CIFAR-binary record file (``label_bytes`` = 1 is the CIFAR-10 layout)."""
+    rec = _pack_records(images, labels, label_bytes)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    rec.tofile(path)
+
+
+def _pack_records(images: np.ndarray, labels: np.ndarray, label_bytes: int) -> np.ndarray:
     lb = _check_label_bytes(label_bytes)
     images = np.ascontiguousarray(images, dtype=np.uint8)
     n = images.shape[0]
@@ -56,8 +71,7 @@ def write_records(path: str, images: np.ndarray, labels: np.ndarray, label_bytes
     for k in range(lb):
         rec[:, k] = (labels >> (8 * k)) & 0xFF
     rec[:, lb:] = images.reshape(n, -1)
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    rec.tofile(path)
+    return rec
 
 
 def _decode_labels(raw: np.ndarray, label_bytes: int) -> np.ndarray:
@@ -80,27 +94,31 @@ def write_synthetic_dataset(out_dir: str, name: str = "cifar10", n_train: int = 
                             shape: Optional[Sequence[int]] = None, label_bytes: int = 1) -> dict:
     """Learnable synthetic dataset in CIFAR-binary layout: class template (low-frequency
     pattern) + per-sample noise, quantised to uint8.  ``shape`` (C, H, W) overrides the shape
-    ``name`` stands for.  Returns a manifest dict."""
+    ``name`` stands for (``imagenet``: 256x256 stored, for the ``"rrc"`` transform to resize).
+    Written in chunks of a few MB of float64 work, so neither the class templates nor the
+    images are ever held whole.  Returns a manifest dict."""
     shape = (tuple(int(v) for v in shape) if shape is not None
-             else {"cifar10": (3, 32, 32), "mnist": (1, 28, 28)}[name])
+             else {"cifar10": (3, 32, 32), "mnist": (1, 28, 28), "imagenet": (3, 256, 256)}[name])
     C, H, W = shape
+    lb = _check_label_bytes(label_bytes)
     rng = np.random.default_rng(seed)
     base = rng.normal(0.0, 1.0, size=(num_classes, C, -(-H // 4), -(-W // 4)))
-    templates = np.kron(base, np.ones((1, 1, 4, 4)))[:, :, :H, :W]
-
-    def make(n, split_seed):
-        r = np.random.default_rng(seed * 1000 + split_seed)
-        y = r.integers(0, num_classes, size=n)
-        x = 0.8 * templates[y] + r.normal(0.0, 1.0, size=(n, C, H, W))
-        img = np.clip(x * 40.0 + 128.0, 0, 255).astype(np.uint8)
-        return img, y
+    chunk = max(1, (1 << 21) // (C * H * W))  # <= 16 MB of float64 per temporary
 
     files = {}
     os.makedirs(out_dir, exist_ok=True)
     for split, n, s in (("train", n_train, 1), ("test", n_test, 2)):
-        img, y = make(n, s)
+        r = np.random.default_rng(seed * 1000 + s)
+        y = r.integers(0, num_classes, size=n)
         path = os.path.join(out_dir, f"{name}_{split}.bin")
-        write_records(path, img, y, label_bytes=label_bytes)
+        with open(path, "wb") as f:
+            # the generator fills draws in order, so chunked draws are the one-call stream
+            for a in range(0, n, chunk):
+                yc = y[a:a + chunk]
+                templates = np.kron(base[yc], np.ones((1, 1, 4, 4)))[:, :, :H, :W]
+                x = 0.8 * templates + r.normal(0.0, 1.0, size=(len(yc), C, H, W))
+                img = np.clip(x * 40.0 + 128.0, 0, 255).astype(np.uint8)
+                _pack_records(img, yc, lb).tofile(f)
         files[split] = path
     return {"name": name, "shape": list(shape), "num_classes": num_classes,
             "label_bytes": int(label_bytes), "n_train": n_train, "n_test": n_test, "files": files}
@@ -152,6 +170,90 @@ def reference_transform(img: np.ndarray, index: int, epoch: int, seed: int, trai
     return (out * (1.0 / (255.0 * s)) + (-m / s)).astype(np.float32)
 
 
+# The "rrc" transform (csrc/common/rrc.hpp holds the native copy of the geometry): aspect ratios
+# w/h in Q16, round(65536 * 0.75 * (16/9) ** (t/63)), log-uniform over [3/4, 4/3].
+RATIO_Q16 = (
+    49152, 49603, 50058, 50517, 50981, 51449, 51921, 52397, 52878, 53363, 53852, 54346, 54845,
+    55348, 55856, 56368, 56886, 57407, 57934, 58466, 59002, 59543, 60090, 60641, 61197, 61759,
+    62325, 62897, 63474, 64057, 64644, 65237, 65836, 66440, 67050, 67665, 68285, 68912, 69544,
+    70182, 70826, 71476, 72132, 72793, 73461, 74135, 74815, 75502, 76195, 76894, 77599, 78311,
+    79030, 79755, 80486, 81225, 81970, 82722, 83481, 84247, 85020, 85800, 86587, 87381)
+RRC_MAX_EXTENT = 32768  # stored and output extents: keeps every Q16 product inside 64 bits
+
+
+def _check_rrc_geometry(H: int, W: int, Ho: int, Wo: int) -> None:
+    if min(H, W) < 2 or min(Ho, Wo) < 1 or max(H, W, Ho, Wo) > RRC_MAX_EXTENT:
+        raise ValueError(f"rrc needs stored extents in [2, {RRC_MAX_EXTENT}] and output extents "
+                         f"in [1, {RRC_MAX_EXTENT}], got {(H, W)} -> {(Ho, Wo)}")
+
+
+def reference_rrc_box(seed: int, epoch: int, index: int, H: int, W: int, train: bool,
+                      flip: bool = True) -> Tuple[int, int, int, int, int]:
+    """(y0, x0, h, w, flip): the source box of the ``"rrc"`` transform, integers only.
+    Training: RandomResizedCrop(scale 0.08-1, ratio 3/4-4/3), ten attempts keyed by splitmix64 of
+    (seed, epoch, index) — the crop transform's word, whose bit 40 is the flip — then the centred
+    ratio-clamped fallback.  Evaluation: the centre square of 7/8 of the short side."""
+    if not train:
+        s = (min(H, W) * 7) // 8
+        return (H - s) // 2, (W - s) // 2, s, s, 0
+    h0 = _splitmix64(seed ^ _splitmix64(((epoch * 0x100000001B3) & _MASK64) ^ (index & _MASK64)))
+    fl = int(bool(flip) and ((h0 >> 40) & 1))
+    for k in range(10):
+        g = _splitmix64((h0 + k + 1) & _MASK64)
+        sq = 5243 + (((65536 - 5243) * (g & 0xFFFFFF)) >> 24)  # scale in Q16 over [0.08, 1)
+        area = (H * W * sq) >> 16
+        r = RATIO_Q16[(g >> 24) & 63]
+        w = math.isqrt((area * r) >> 16)
+        h = math.isqrt((area << 16) // r)
+        if 0 < w <= W and 0 < h <= H:
+            g2 = _splitmix64(g)
+            return (g2 & 0xFFFFFFFF) % (H - h + 1), (g2 >> 32) % (W - w + 1), h, w, fl
+    h, w = H, W
+    if 4 * W < 3 * H:
+        h = (4 * W) // 3
+    elif 3 * W > 4 * H:
+        w = (4 * H) // 3
+    return (H - h) // 2, (W - w) // 2, h, w, fl
+
+
+def _rrc_taps(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """(i0, i1, l0, l1) of every output coordinate of an axis resampled from n_in to n_out:
+    half-pixel centres in Q16, floored; the weights are exact float32."""
+    o = np.arange(n_out, dtype=np.int64)
+    p = np.maximum((((2 * o + 1) * n_in) << 15) // n_out - 32768, 0)
+    i0 = p >> 16
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    l1 = (p & 0xFFFF).astype(np.float32) * np.float32(2.0 ** -16)
+    return i0, i1, np.float32(1.0) - l1, l1
+
+
+def reference_transform_rrc(img: np.ndarray, index: int, epoch: int, seed: int, train: bool,
+                            out_size: Sequence[int], flip: bool, mean, std) -> np.ndarray:
+    """NumPy definition of the ``"rrc"`` per-sample transform (uint8 CHW -> float32 [C, Ho, Wo]):
+    the :func:`reference_rrc_box` box resampled bilinearly to ``out_size``, flipped, normalised.
+    The horizontal blend of 8-bit pixels with Q16 weights is exact in float32; the vertical one is
+    two rounded multiplies and a rounded add; then ``v * scale + offset`` as in
+    :func:`reference_transform`.  The native loader and the device kernel match it bit for bit."""
+    C, H, W = img.shape
+    Ho, Wo = (int(v) for v in out_size)
+    _check_rrc_geometry(H, W, Ho, Wo)
+    y0, x0, h, w, fl = reference_rrc_box(seed, epoch, index, H, W, train, flip)
+    ry0, ry1, ly0, ly1 = _rrc_taps(h, Ho)
+    cx0, cx1, lx0, lx1 = _rrc_taps(w, Wo)
+    if fl:  # output column ox takes the taps of column Wo-1-ox
+        cx0, cx1, lx0, lx1 = cx0[::-1], cx1[::-1], lx0[::-1], lx1[::-1]
+    box = img[:, y0:y0 + h, x0:x0 + w].astype(np.float32)
+    r0, r1 = box[:, ry0], box[:, ry1]
+    top = r0[:, :, cx0] * lx0 + r0[:, :, cx1] * lx1
+    bot = r1[:, :, cx0] * lx0 + r1[:, :, cx1] * lx1
+    a = top * ly0[None, :, None]
+    b = bot * ly1[None, :, None]
+    v = a + b
+    m = np.asarray(mean, np.float32)[:, None, None]
+    s = np.asarray(std, np.float32)[:, None, None]
+    return (v * (1.0 / (255.0 * s)) + (-m / s)).astype(np.float32)
+
+
 class RecordDataLoader:
     """Iterates (x [B,C,H,W] float32, y [B] int64) batches of this rank's shard.
 
@@ -163,20 +265,40 @@ class RecordDataLoader:
     mode), the records and their sample indices are uploaded (a quarter of the bytes) and
     ``ops.kernels.record_decode`` runs the same transform on ``device`` — the same bits as the
     host path.  ``out_dtype``: dtype of ``x`` (float32 or bfloat16).  ``label_bytes``: width of
-    the little-endian label in front of every record."""
+    the little-endian label in front of every record.
+
+    ``transform="crop"`` (default) is RandomCrop(``pad``) + flip + Normalize at the stored size.
+    ``transform="rrc"`` is :func:`reference_transform_rrc`: RandomResizedCrop + flip + Normalize
+    in training, a 7/8 centre crop in evaluation, resized to ``out_size`` = (Ho, Wo) (default: the
+    stored size); ``pad`` is not used.  Both work with either ``decode``."""
 
     def __init__(self, files: Sequence[str], shape: Sequence[int], batch_size: int,
                  sampler: Optional[DistributedSampler] = None, train: bool = True,
                  pad: int = 4, flip: bool = True, mean=CIFAR10_MEAN, std=CIFAR10_STD,
                  seed: int = 0, workers: int = 8, prefetch: int = 4, drop_last: bool = False,
                  device: Optional[torch.device] = None, decode: str = "host",
-                 out_dtype: torch.dtype = torch.float32, label_bytes: int = 1):
+                 out_dtype: torch.dtype = torch.float32, label_bytes: int = 1,
+                 transform: str = "crop", out_size: Optional[Sequence[int]] = None):
         from mipipe.runtime import runtime, runtime_available
         if decode not in ("host", "device"):
             raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
         if out_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
-        self.shape = tuple(shape)
+        if transform not in ("crop", "rrc"):
+            raise ValueError(f"transform must be 'crop' or 'rrc', got {transform!r}")
+        self.shape = tuple(int(v) for v in shape)
+        self.transform = transform
+        if transform == "crop":
+            if out_size is not None and tuple(out_size) != self.shape[1:]:
+                raise ValueError("out_size needs transform='rrc' (the crop transform keeps the "
+                                 "stored size)")
+            self.out_size = self.shape[1:]
+        else:
+            self.out_size = (tuple(int(v) for v in out_size) if out_size is not None
+                             else self.shape[1:])
+            if len(self.out_size) != 2:
+                raise ValueError(f"out_size must be (Ho, Wo), got {out_size!r}")
+            _check_rrc_geometry(*self.shape[1:], *self.out_size)
         self.batch_size = batch_size
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         self.train, self.pad, self.flip = train, pad, flip
@@ -198,6 +320,9 @@ class RecordDataLoader:
             cfg.mean, cfg.std = list(map(float, mean)), list(map(float, std))
             cfg.seed, cfg.workers, cfg.prefetch, cfg.drop_last = seed, workers, prefetch, drop_last
             cfg.raw = decode == "device"
+            if transform == "rrc":
+                cfg.transform = "rrc"
+                cfg.out_h, cfg.out_w = self.out_size
             self._ld = runtime().RecordLoader(cfg)
             n = len(self._ld)
         else:
@@ -223,7 +348,9 @@ class RecordDataLoader:
                             torch.empty(batch_size, dtype=torch.int64, pin_memory=pin))
                            for _ in range(2)]
         else:
-            self._stage = [(torch.empty(batch_size, C, H, W, dtype=torch.float32, pin_memory=pin),
+            Ho, Wo = self.out_size
+            self._stage = [(torch.empty(batch_size, C, Ho, Wo, dtype=torch.float32,
+                                        pin_memory=pin),
                             torch.empty(batch_size, dtype=torch.int64, pin_memory=pin))
                            for _ in range(2)]
 
@@ -261,12 +388,19 @@ class RecordDataLoader:
         else:
             for b in range(len(self)):
                 sl = idx[b * self.batch_size:(b + 1) * self.batch_size]
-                x = np.stack([reference_transform(self._imgs[i], i, self.epoch, self.seed,
-                                                  self.train, self.pad if self.train else 0,
-                                                  self.flip and self.train, self.mean, self.std)
-                              for i in sl])
+                x = np.stack([self._reference(i) for i in sl])
                 yield self._cast(self._to_device(torch.from_numpy(x),
                                                  torch.from_numpy(self._labels[sl])))
+
+    def _reference(self, i: int) -> np.ndarray:
+        """Sample ``i`` through the NumPy definition of the configured transform."""
+        if self.transform == "rrc":
+            return reference_transform_rrc(self._imgs[i], i, self.epoch, self.seed, self.train,
+                                           self.out_size, self.flip and self.train, self.mean,
+                                           self.std)
+        return reference_transform(self._imgs[i], i, self.epoch, self.seed, self.train,
+                                   self.pad if self.train else 0, self.flip and self.train,
+                                   self.mean, self.std)
 
     def _iter_device(self, idx) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         """decode="device": upload the uint8 records + sample indices, transform on the device."""
@@ -274,6 +408,10 @@ class RecordDataLoader:
         epoch = self.epoch
 
         def decode(rec, gi):
+            if self.transform == "rrc":
+                return K.record_decode_rrc(rec, gi, self._affine, self.shape, self.out_size,
+                                           self.seed, epoch, self.flip and self.train, self.train,
+                                           self.label_bytes, self.out_dtype)
             return K.record_decode(rec, gi, self._affine, self.shape, self.seed, epoch,
                                    self.pad if self.train else 0, self.flip and self.train,
                                    self.train, self.label_bytes, self.out_dtype)

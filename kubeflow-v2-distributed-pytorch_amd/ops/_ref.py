@@ -537,3 +537,54 @@ def record_decode(rec: Tensor, idx: Tensor, affine: Tensor, shape, seed: int, ep
     x = out * sc
     x = x + off
     return x.to(dtype), y
+
+
+def record_decode_rrc(rec: Tensor, idx: Tensor, affine: Tensor, shape, out_size, seed: int,
+                      epoch: int, flip: bool, train: bool, label_bytes: int = 1,
+                      dtype=torch.float32) -> Tuple[Tensor, Tensor]:
+    """The record loader's ``"rrc"`` transform on whole records (csrc/kernels/records.hip's
+    record_decode_rrc contract): inputs as :func:`record_decode`, x is [n, C, Ho, Wo].  Per sample
+    the integer box of ``data.records.reference_rrc_box`` is resampled bilinearly with the Q16
+    taps of ``data.records._rrc_taps`` (flip = taps of the mirrored column): the horizontal
+    blends are exact, the vertical one is two rounded multiplies and a rounded add, then
+    ``v * scale`` and ``+ offset`` — the same bits as ``reference_transform_rrc``."""
+    import numpy as np
+    from mipipe.data.records import _check_rrc_geometry, _rrc_taps, reference_rrc_box
+    C, H, W = shape
+    Ho, Wo = out_size
+    _check_rrc_geometry(H, W, Ho, Wo)
+    n = rec.shape[0]
+    dev = rec.device
+    y = torch.zeros(n, dtype=torch.int64, device=dev)
+    for k in range(label_bytes):
+        y |= rec[:, k].long() << (8 * k)
+    rows = np.zeros((2, n, Ho), np.int64)
+    cols = np.zeros((2, n, Wo), np.int64)
+    wy = np.zeros((2, n, Ho), np.float32)
+    wx = np.zeros((2, n, Wo), np.float32)
+    for s, gi in enumerate(idx.tolist()):
+        y0, x0, h, w, fl = reference_rrc_box(seed, epoch, gi, H, W, train, flip)
+        r0, r1, l0, l1 = _rrc_taps(h, Ho)
+        rows[0, s], rows[1, s], wy[0, s], wy[1, s] = r0 + y0, r1 + y0, l0, l1
+        c0, c1, l0, l1 = _rrc_taps(w, Wo)
+        if fl:
+            c0, c1, l0, l1 = c0[::-1], c1[::-1], l0[::-1], l1[::-1]
+        cols[0, s], cols[1, s], wx[0, s], wx[1, s] = c0 + x0, c1 + x0, l0, l1
+    rows, cols = torch.from_numpy(rows).to(dev), torch.from_numpy(cols).to(dev)
+    wy, wx = torch.from_numpy(wy).to(dev), torch.from_numpy(wx).to(dev)
+    img = rec[:, label_bytes:].reshape(n, C, H, W).float()
+    ar_n = torch.arange(n, device=dev)[:, None, None, None]
+    ar_c = torch.arange(C, device=dev)[None, :, None, None]
+
+    def tap(r, c):
+        return img[ar_n, ar_c, rows[r][:, None, :, None], cols[c][:, None, None, :]]
+
+    lx0, lx1 = wx[0][:, None, None, :], wx[1][:, None, None, :]
+    top = tap(0, 0) * lx0 + tap(0, 1) * lx1
+    bot = tap(1, 0) * lx0 + tap(1, 1) * lx1
+    a = top * wy[0][:, None, :, None]
+    b = bot * wy[1][:, None, :, None]
+    v = a + b
+    x = v * affine[0].float().view(1, C, 1, 1)
+    x = x + affine[1].float().view(1, C, 1, 1)
+    return x.to(dtype), y

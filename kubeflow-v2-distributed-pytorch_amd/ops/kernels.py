@@ -20,7 +20,8 @@ __all__ = ["conv_fwd", "conv_dgrad", "conv_wgrad", "bn_finalize", "bn_act_fwd",
            "avgpool_fwd", "avgpool_bwd", "pool_bn_fwd", "pool_bn_bwd", "pool_bn_supported", "stem_fused_supported", "stem_fwd_stats",
            "stem_fwd_pool", "stem_bwd", "gemm", "cross_entropy_fwd_bwd", "top1_correct", "sgd_step",
            "adamw_step", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
-           "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "record_decode", "use_native",
+           "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "record_decode", "record_decode_rrc",
+           "use_native",
            "gconv_fwd", "gconv_dgrad", "gconv_wgrad", "chan_stats", "affine_act",
            "bn_generic_bwd_reduce", "bn_generic_bwd_apply", "avgpool2d_fwd", "avgpool2d_bwd"]
 
@@ -571,6 +572,22 @@ def record_decode(rec, idx, affine, shape, seed: int, epoch: int, pad: int, flip
                                       bool(flip), bool(train), int(label_bytes), dtype)
     return _ref.record_decode(rec, idx, affine, (C, H, W), int(seed), int(epoch), int(pad),
                               bool(flip), bool(train), int(label_bytes), dtype)
+
+
+def record_decode_rrc(rec, idx, affine, shape, out_size, seed: int, epoch: int, flip: bool,
+                      train: bool, label_bytes: int = 1, dtype=torch.float32):
+    """The record loader's ``"rrc"`` transform on whole uint8 records (inputs as
+    :func:`record_decode`): RandomResizedCrop + flip + Normalize in training, a 7/8 centre crop
+    otherwise, resized bilinearly to ``out_size`` = (Ho, Wo) -> (x [n, C, Ho, Wo] fp32 / bf16,
+    y [n] int64), bit-identical to the host loader's output."""
+    C, H, W = (int(v) for v in shape)
+    Ho, Wo = (int(v) for v in out_size)
+    if use_native(rec):
+        return native().record_decode_rrc(rec, idx, affine, C, H, W, Ho, Wo, int(seed),
+                                          int(epoch), bool(flip), bool(train), int(label_bytes),
+                                          dtype)
+    return _ref.record_decode_rrc(rec, idx, affine, (C, H, W), (Ho, Wo), int(seed), int(epoch),
+                                  bool(flip), bool(train), int(label_bytes), dtype)
 
 
 # ----------------------------------------------------------------------------- vision.hip

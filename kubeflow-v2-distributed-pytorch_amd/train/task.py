@@ -186,6 +186,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device-decode", type=int, choices=[0, 1], default=0,
                    help="with --data-dir: 1 uploads the uint8 records and crops / flips / "
                         "normalises them on the device (same bits as the host loader's output)")
+    p.add_argument("--record-transform", choices=["crop", "rrc"], default=None,
+                   help="with --data-dir: crop = RandomCrop(padding) + flip at the stored size; "
+                        "rrc = RandomResizedCrop + flip (7/8 centre crop for evaluation) resized "
+                        "to the model's input size. Default: crop, or rrc when the data "
+                        "directory's manifest.json stores another size than the model takes")
     p.add_argument("--train-samples", type=int, default=None)
     p.add_argument("--test-samples", type=int, default=None)
     p.add_argument("--num_classes", type=int, default=None,
@@ -217,6 +222,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--cpu-procs", type=int, default=1,
                    help="processes per node when no GPU is visible (gloo)")
     return p
+
+
+def _read_manifest(data_dir: str):
+    """The dict of ``<data_dir>/manifest.json`` (shape, label_bytes, num_classes, ...) or None."""
+    path = os.path.join(data_dir, "manifest.json") if data_dir else ""
+    if not path or not os.path.isfile(path):
+        return None
+    with open(path) as f:
+        man = json.load(f)
+    if len(man.get("shape", ())) != 3:
+        raise ValueError(f"{path}: 'shape' must be [C, H, W]")
+    return man
 
 
 def _ngpus() -> int:
@@ -310,6 +327,19 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
     C, H, W, K, N = DATASET_SHAPES[args.dataset]
     if args.image_size:
         H = W = args.image_size
+    # records: a manifest.json next to them (the pipeline's preprocess step writes one) carries
+    # the stored shape, the label width and the class count; explicit flags win
+    manifest = _read_manifest(args.data_dir)
+    stored, label_bytes = (C, H, W), 1
+    if manifest is not None:
+        stored = tuple(int(v) for v in manifest["shape"])
+        label_bytes = int(manifest.get("label_bytes", 1))
+        C = stored[0]
+        if args.num_classes is None and "num_classes" in manifest:
+            args.num_classes = int(manifest["num_classes"])
+    record_transform = args.record_transform or ("rrc" if stored[1:] != (H, W) else "crop")
+    if record_transform == "crop":
+        H, W = stored[1:]  # the crop transform keeps the stored size
     kw = {}
     if args.num_classes is not None:
         kw["num_classes"] = args.num_classes
@@ -369,20 +399,28 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         # task.py:246-267: RandomCrop(32, 4) + flip + Normalize, DistributedSampler shards,
         # test loader batch 128 unshuffled — on the native multi-threaded loader
         from mipipe.data import records as REC
-        mean, std = ((REC.MNIST_MEAN, REC.MNIST_STD) if args.dataset == "mnist"
-                     else (REC.CIFAR10_MEAN, REC.CIFAR10_STD))
+        mean, std = {"mnist": (REC.MNIST_MEAN, REC.MNIST_STD),
+                     "imagenet": (REC.IMAGENET_MEAN, REC.IMAGENET_STD)}.get(
+                         args.dataset, (REC.CIFAR10_MEAN, REC.CIFAR10_STD))
+        if manifest is not None and "mean" in manifest and "std" in manifest:
+            mean, std = tuple(manifest["mean"]), tuple(manifest["std"])
         pad = 4 if args.dataset == "cifar10" else 0
         decode = "device" if args.device_decode else "host"
-        probe = REC.RecordDataLoader(train_files, (C, H, W), args.batch_size, train=True,
+        # rrc: RandomResizedCrop + flip (train) / 7/8 centre crop (test) to the model's size
+        rkw = {"label_bytes": label_bytes}
+        if record_transform == "rrc":
+            rkw.update(transform="rrc", out_size=(H, W))
+        probe = REC.RecordDataLoader(train_files, stored, args.batch_size, train=True,
                                      pad=pad, mean=mean, std=std, seed=args.random_seed,
-                                     workers=max(1, args.workers), device=device, decode=decode)
+                                     workers=max(1, args.workers), device=device, decode=decode,
+                                     **rkw)
         train_sampler = DistributedSampler(probe.num_samples_total, seed=args.random_seed)
         probe.sampler = train_sampler
         train_loader = probe
         tfiles = test_files or train_files
-        test_loader = REC.RecordDataLoader(tfiles, (C, H, W), 128, train=False, mean=mean,
+        test_loader = REC.RecordDataLoader(tfiles, stored, 128, train=False, mean=mean,
                                            std=std, workers=max(1, args.workers), device=device,
-                                           decode=decode)
+                                           decode=decode, **rkw)
         test_sampler = DistributedSampler(test_loader.num_samples_total, shuffle=False)
         test_loader.sampler = test_sampler
     else:

@@ -43,9 +43,10 @@ def _newest_header() -> float:
 def sources_digest(kind: str) -> str:
     """SHA-256 over the sources (paths + bytes) a library is built from."""
     if kind == "C":
-        pats = ["kernels/*.hip", "kernels/*.hpp", "bindings.cpp", "comm/*.cpp", "comm/*.h*"]
+        pats = ["kernels/*.hip", "kernels/*.hpp", "bindings.cpp", "comm/*.cpp", "comm/*.h*",
+                "common/*.h*"]
     else:
-        pats = ["runtime/*.cpp", "runtime/*.h*"]
+        pats = ["runtime/*.cpp", "runtime/*.h*", "common/*.h*"]  # common/: host + device headers
     files = sorted({f for p in pats for f in glob.glob(os.path.join(CSRC, p))})
     h = hashlib.sha256()
     for f in files:

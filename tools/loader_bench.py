@@ -8,8 +8,14 @@ run in the same process on the same files, alternated ``--reps`` times; each tim
 excludes its warm-up iterations.  Prints one JSON line per measurement and a summary line (median
 img/s per mode and the GPU's clocks sampled during the run); ``--out`` also writes them to a file.
 
+``--transform rrc --record-size S --image-size R`` measures the resizing transform instead
+(SxS records with 2-byte labels, RandomResizedCrop to RxR; ``--dtype bf16`` for bf16 batches):
+the loader alone by default, ``--train-step 1`` adds the ResNet-18 loop.
+
 Usage: python tools/loader_bench.py [--n 51200] [--batch 1024] [--workers 8] [--reps 3]
                                     [--out profiles/loader_bench.txt]
+       python tools/loader_bench.py --transform rrc --record-size 256 --image-size 224 \
+                                    --n 2048 --batch 256 --dtype bf16
 """
 from __future__ import annotations
 
@@ -36,6 +42,12 @@ def main(argv=None) -> int:
     ap.add_argument("--warmup", type=int, default=5, help="untimed batches / steps per loop")
     ap.add_argument("--min-seconds", type=float, default=1.5,
                     help="a measurement repeats whole epochs until this much time has passed")
+    ap.add_argument("--transform", choices=["crop", "rrc"], default="crop")
+    ap.add_argument("--record-size", type=int, default=256, help="rrc: stored H = W")
+    ap.add_argument("--image-size", type=int, default=224, help="rrc: output H = W")
+    ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32", help="batch dtype")
+    ap.add_argument("--train-step", type=int, choices=[0, 1], default=None,
+                    help="also time a ResNet-18 training step per batch (default: crop only)")
     ap.add_argument("--data-dir", default="", help="reuse / keep the record files here")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
@@ -61,19 +73,28 @@ def main(argv=None) -> int:
     if not data_dir:
         tmp = tempfile.TemporaryDirectory(prefix="loader_bench_")
         data_dir = tmp.name
-    files = R.dataset_files(data_dir, "cifar10", "train")
+    rrc = a.transform == "rrc"
+    name = "imagenet" if rrc else "cifar10"
+    shape = (3, a.record_size, a.record_size) if rrc else (3, 32, 32)
+    out_dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    train_step = bool(a.train_step) if a.train_step is not None else not rrc
+    files = R.dataset_files(data_dir, name, "train")
     if not files:
-        R.write_synthetic_dataset(data_dir, "cifar10", n_train=a.n, n_test=16, seed=0)
-        files = R.dataset_files(data_dir, "cifar10", "train")
+        R.write_synthetic_dataset(data_dir, name, n_train=a.n, n_test=16, seed=0, shape=shape,
+                                  num_classes=1000 if rrc else 10, label_bytes=2 if rrc else 1)
+        files = R.dataset_files(data_dir, name, "train")
 
-    loaders = {m: R.RecordDataLoader(files, (3, 32, 32), a.batch, train=True, pad=4, seed=0,
-                                     workers=a.workers, prefetch=a.prefetch, device=dev, decode=m)
+    kw = (dict(transform="rrc", out_size=(a.image_size, a.image_size), label_bytes=2,
+               mean=R.IMAGENET_MEAN, std=R.IMAGENET_STD) if rrc else dict(pad=4))
+    loaders = {m: R.RecordDataLoader(files, shape, a.batch, train=True, seed=0, workers=a.workers,
+                                     prefetch=a.prefetch, device=dev, decode=m,
+                                     out_dtype=out_dtype, **kw)
                for m in ("host", "device")}
     n_total = loaders["host"].num_samples_total
 
     torch.manual_seed(0)
-    model = create_model("resnet18", num_classes=10, in_chans=3).to(dev)
-    model.compute_dtype = torch.float32
+    model = create_model("resnet18", num_classes=1000 if rrc else 10, in_chans=3).to(dev)
+    model.compute_dtype = out_dtype
     opt = SGD(model.parameters(), 0.1, momentum=0.9, weight_decay=1e-4)
     model.train()
 
@@ -117,21 +138,24 @@ def main(argv=None) -> int:
     res = {(m, t): [] for m in loaders for t in (False, True)}
     epoch = 0
     with ClockSampler(dev.index or 0) as cs:
-        for train in (False, True):
+        for train in ((False, True) if train_step else (False,)):
             for rep in range(a.reps):
                 for mode in ("host", "device"):
                     v, epoch = run(mode, train, epoch)
                     res[(mode, train)].append(v)
-                    emit({"what": "resnet18_fp32_step" if train else "loader_alone",
+                    emit({"what": f"resnet18_{a.dtype}_step" if train else "loader_alone",
                           "decode": mode, "rep": rep, "img_per_s": round(v, 1)})
     med = {f"{'train' if t else 'loader'}_{m}": round(statistics.median(v), 1)
-           for (m, t), v in res.items()}
-    emit({"summary": med, "records": n_total, "batch": a.batch, "workers": a.workers,
+           for (m, t), v in res.items() if v}
+    emit({"summary": med, "transform": a.transform, "record_shape": list(shape),
+          "out_size": [a.image_size] * 2 if rrc else list(shape[1:]), "dtype": a.dtype,
+          "records": n_total, "batch": a.batch, "workers": a.workers,
           "prefetch": a.prefetch, "warmup_batches": a.warmup, "reps": a.reps,
           "host_cpus": len(os.sched_getaffinity(0)), "gpu": torch.cuda.get_device_name(0),
           "min_seconds": a.min_seconds, "gpu_clocks": cs.summary(),
           "loader_speedup": round(med["loader_device"] / med["loader_host"], 2),
-          "train_speedup": round(med["train_device"] / med["train_host"], 2)})
+          **({"train_speedup": round(med["train_device"] / med["train_host"], 2)}
+             if train_step else {})})
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

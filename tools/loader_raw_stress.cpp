@@ -6,7 +6,10 @@
 // It writes two record files, then drives a raw-mode loader with several workers through
 // start_epoch generations — complete epochs, an epoch abandoned half way (the next generation
 // starts while workers are still filling slots) and a partial last batch — and checks every
-// byte and index that next_raw returns.  Exit status 0 = all checks passed.
+// byte and index that next_raw returns.  A last section drives the host "rrc" transform
+// (fill_rrc: float slots sized for the output, not the stored shape) the same way, down- and
+// up-scaling, and checks every value against the taps of common/rrc.hpp.
+// Exit status 0 = all checks passed.
 #include <unistd.h>
 
 #include <cstdio>
@@ -15,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "../common/rrc.hpp"
 #include "runtime.hpp"
 
 using namespace mipipe_rt;
@@ -64,6 +68,67 @@ static int64_t consume(RecordLoader& ld, const std::vector<int64_t>& order, int 
     seen += n;
   }
   return seen;
+}
+
+// the rrc value of one output element, recomputed from the definition (mean 0, std 1)
+static float rrc_value(int64_t gi, int c, int oy, int ox, int H, int W, int Ho, int Wo,
+                       size_t label_bytes, uint64_t seed, uint64_t epoch, bool train) {
+  const mipipe_rrc::Box bx = mipipe_rrc::rrc_box(seed, epoch, (uint64_t)gi, H, W, train, train);
+  const mipipe_rrc::Tap ty = mipipe_rrc::rrc_tap(oy, bx.h, Ho);
+  const mipipe_rrc::Tap tx = mipipe_rrc::rrc_tap(bx.flip ? Wo - 1 - ox : ox, bx.w, Wo);
+  auto px = [&](int y, int x) {
+    return (float)byte_of(gi, label_bytes + ((size_t)c * H + (bx.y0 + y)) * W + (bx.x0 + x));
+  };
+  const float lx1 = (float)tx.frac / 65536.f, lx0 = 1.f - lx1;
+  const float ly1 = (float)ty.frac / 65536.f, ly0 = 1.f - ly1;
+  const float top = px(ty.i0, tx.i0) * lx0 + px(ty.i0, tx.i1) * lx1;
+  const float bot = px(ty.i1, tx.i0) * lx0 + px(ty.i1, tx.i1) * lx1;
+  const float a = top * ly0, b = bot * ly1;
+  return (a + b) * (1.f / 255.f);
+}
+
+static void rrc_section(LoaderConfig cfg, int Ho, int Wo, bool train, int64_t total) {
+  cfg.raw = false;
+  cfg.train = train;
+  cfg.flip = train;
+  cfg.transform = "rrc";
+  cfg.out_h = Ho;
+  cfg.out_w = Wo;
+  cfg.seed = 11;
+  RecordLoader ld(cfg);
+  const size_t per = (size_t)cfg.C * Ho * Wo;
+  std::vector<float> x((size_t)cfg.batch * per);
+  std::vector<int64_t> y(cfg.batch);
+  std::vector<int64_t> order(total);
+  std::iota(order.begin(), order.end(), 0);
+  for (int round = 0; round < 12; ++round) {
+    for (int64_t i = total - 1; i > 0; --i) std::swap(order[i], order[(i * 7919 + round * 31) % (i + 1)]);
+    ld.start_epoch(order, round);
+    int64_t seen = 0;
+    for (int b = 0; round % 3 != 1 || b < 2; ++b) {  // every third epoch is abandoned mid-way
+      const int n = ld.next(x.data(), y.data());
+      if (n == 0) break;
+      for (int s = 0; s < n; ++s) {
+        const int64_t gi = order[seen + s];
+        int64_t label = 0;
+        for (int k = 0; k < cfg.label_bytes; ++k) label |= (int64_t)byte_of(gi, k) << (8 * k);
+        CHECK(y[s] == label);
+        for (int c = 0; c < cfg.C; ++c)
+          for (int oy = 0; oy < Ho; ++oy)
+            for (int ox = 0; ox < Wo; ++ox) {
+              const float want = rrc_value(gi, c, oy, ox, cfg.H, cfg.W, Ho, Wo, cfg.label_bytes,
+                                           cfg.seed, (uint64_t)round, train);
+              if (x[(size_t)s * per + ((size_t)c * Ho + oy) * Wo + ox] != want) {
+                CHECK(!"rrc value mismatch");
+                ox = Wo; oy = Ho; c = cfg.C;
+              }
+            }
+      }
+      seen += n;
+    }
+    CHECK(round % 3 == 1 ? seen == 2 * cfg.batch : seen == total);
+  }
+  ld.start_epoch(order, 100);  // destroyed with workers busy
 }
 
 int main() {
@@ -121,6 +186,9 @@ int main() {
     CHECK(ld.batches_per_epoch() == total / batch);
     CHECK(consume(ld, order, batch, rec_bytes, -1) == (total / batch) * batch);
   }
+  rrc_section(cfg, 5, 7, true, total);    // 8x8 boxes down and up to odd extents
+  rrc_section(cfg, 19, 13, true, total);  // output larger than the stored image
+  rrc_section(cfg, 6, 6, false, total);   // evaluation: centre 7x7 -> 6x6
   for (auto& f : cfg.files) unlink(f.c_str());
   std::printf(g_fail ? "loader_raw_stress: %d check(s) FAILED\n" : "loader_raw_stress: ok\n", g_fail);
   return g_fail ? 1 : 0;
