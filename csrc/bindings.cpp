@@ -355,6 +355,56 @@ std::tuple<Tensor, optional<Tensor>, optional<Tensor>> conv_fwd(Tensor x, Tensor
   return {y, ps, pss};
 }
 
+// Inference forward: y = act(conv(x, w) * scale + shift + residual) in the conv's epilogue
+// (conv_infer.hip) — an eval-mode BatchNorm folded to (scale, shift) by bn_fold_affine, the
+// block's residual and its ReLU.  Plans are tuned under their own keys: the candidates are the
+// plain forward's, the epilogue (and so the best tile) is not.
+Tensor conv_fwd_infer(Tensor x, Tensor w, int stride, int pad, optional<Tensor> scale,
+                      optional<Tensor> shift, optional<Tensor> residual, bool relu, int stride_w,
+                      int pad_w, int cfg) {
+  check_act(x, "x");
+  check_same(w, x, "w");
+  c10::DeviceGuard g(x.device());
+  auto s = conv_shape(x, w, stride, pad, stride_w, pad_w);
+  s.f32 = is_f32(x);
+  auto vec = [&](const optional<Tensor>& t, const char* name) -> const float* {
+    if (!t.has_value()) return nullptr;
+    check_vec(*t, s.Co, name);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+    return t->data_ptr<float>();
+  };
+  const float* scp = vec(scale, "scale");
+  const float* shp = vec(shift, "shift");
+  auto y = torch::empty({s.N, s.Ho, s.Wo, s.Co}, x.options());
+  const void* rp = nullptr;
+  if (residual.has_value()) {
+    check_same(*residual, x, "residual");
+    TORCH_CHECK(residual->sizes() == y.sizes(), "residual must have the output's shape ", y.sizes(),
+                ", got ", residual->sizes());
+    rp = residual->data_ptr();
+  }
+  auto split_ws = [&](int plan) -> Tensor {  // fp32 workspace of a split-K plan (else empty)
+    const long n = mipipe::conv_fwd_split_ws_elems(s, plan);
+    return n > 0 ? torch::empty({n}, x.options().dtype(at::kFloat)) : Tensor();
+  };
+  auto wsp = [](const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
+  if (cfg < 0) {
+    const long M = (long)s.N * s.Ho * s.Wo;
+    const int nk = (int)(((long)s.KH * s.KW * s.Ci + 63) / 64);
+    cfg = tune::select_from(tune::key(rp != nullptr ? "fwdinfr" : "fwdinf", s),
+                            tune::conv_plan_candidates(s.f32, M, s.Co, nk), [&](int c) {
+      auto ys = torch::empty_like(y);
+      Tensor ws = split_ws(c);
+      mipipe::conv_fwd_infer(x.data_ptr(), w.data_ptr(), ys.data_ptr(), s, stream(), scp, shp, rp,
+                             relu, c, wsp(ws));
+    });
+  }
+  Tensor ws = split_ws(cfg);
+  mipipe::conv_fwd_infer(x.data_ptr(), w.data_ptr(), y.data_ptr(), s, stream(), scp, shp, rp, relu,
+                         cfg, wsp(ws));
+  return y;
+}
+
 Tensor conv_dgrad(Tensor dy, Tensor w, std::vector<int64_t> x_shape, int stride, int pad,
                   optional<Tensor> addend, optional<Tensor> bn_y, optional<Tensor> bn_mean,
                   optional<Tensor> bn_invstd, optional<Tensor> bn_scale, optional<Tensor> bn_bias,
@@ -697,6 +747,27 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> bn_finalize(Tensor psum, Tensor psq, 
                       scale.data_ptr<float>(), bias.data_ptr<float>(), zero_after, nbt_p,
                       stream());
   return {mean, invstd, scale, bias};
+}
+
+// Eval-mode BatchNorm (+ the producing conv's bias) as (scale, shift), one launch
+std::tuple<Tensor, Tensor> bn_fold_affine(Tensor gamma, Tensor beta, Tensor rm, Tensor rv,
+                                          double eps, optional<Tensor> conv_bias) {
+  check_f32(gamma, "weight");
+  c10::DeviceGuard g(gamma.device());
+  const int64_t C = gamma.numel();
+  check_vec(beta, C, "bias");
+  check_vec(rm, C, "running_mean");
+  check_vec(rv, C, "running_var");
+  if (conv_bias.has_value()) check_vec(*conv_bias, C, "conv_bias");
+  // one allocation, rows 16-B aligned for the conv epilogue's vector loads
+  const int64_t Cp = (C + 3) / 4 * 4;
+  auto st2 = torch::empty({2, Cp}, gamma.options());
+  auto scale = st2[0].narrow(0, 0, C), shift = st2[1].narrow(0, 0, C);
+  mipipe::bn_fold_affine(gamma.data_ptr<float>(), beta.data_ptr<float>(), rm.data_ptr<float>(),
+                         rv.data_ptr<float>(),
+                         conv_bias.has_value() ? conv_bias->data_ptr<float>() : nullptr, (float)eps,
+                         (int)C, scale.data_ptr<float>(), shift.data_ptr<float>(), stream());
+  return {scale, shift};
 }
 
 Tensor bn_act_fwd(Tensor y, Tensor scale, Tensor bias, bool relu, optional<Tensor> r,
@@ -2105,6 +2176,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("stride_w") = 0, py::arg("pad_w") = -1, py::arg("cfg") = -1,
         py::arg("wflip") = py::none(), py::arg("in_scale") = py::none(),
         py::arg("in_bias") = py::none());
+  m.def("conv_fwd_infer", &conv_fwd_infer, py::arg("x"), py::arg("w"), py::arg("stride"),
+        py::arg("pad"), py::arg("scale") = py::none(), py::arg("shift") = py::none(),
+        py::arg("residual") = py::none(), py::arg("relu") = false, py::arg("stride_w") = 0,
+        py::arg("pad_w") = -1, py::arg("cfg") = -1);
   m.attr("STAT_REPLICAS") = mipipe::kStatReplicas;
   m.def("conv_dgrad", &conv_dgrad, py::arg("dy"), py::arg("w"), py::arg("x_shape"),
         py::arg("stride"), py::arg("pad"), py::arg("addend") = py::none(),
@@ -2166,6 +2241,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("shift"), py::arg("gamma"), py::arg("beta"), py::arg("rm"), py::arg("rv"),
         py::arg("momentum"), py::arg("eps"), py::arg("zero_after") = true,
         py::arg("nbt") = py::none());
+  m.def("bn_fold_affine", &bn_fold_affine, py::arg("weight"), py::arg("bias"),
+        py::arg("running_mean"), py::arg("running_var"), py::arg("eps"),
+        py::arg("conv_bias") = py::none());
   m.def("bn_act_fwd", &bn_act_fwd, py::arg("y"), py::arg("scale"), py::arg("bias"),
         py::arg("relu"), py::arg("r"), py::arg("rscale"), py::arg("rbias"),
         py::arg("mask") = py::none());

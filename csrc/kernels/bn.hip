@@ -203,6 +203,28 @@ void bn_finalize(float* psum, float* psq, int P, int C, long count, const float*
                      run_var, momentum, eps, mean, invstd, scale, bias, zero_after, nbt);
 }
 
+// Eval mode: the running statistics make BatchNorm a fixed per-channel affine, which the
+// inference conv epilogue applies (conv_infer.hip).  A bias of the producing conv folds into the
+// shift.  One launch instead of the rsqrt / mul / mul / sub ATen ops (and the y + bias pass).
+__global__ void bn_fold_affine_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                      const float* __restrict__ mean, const float* __restrict__ var,
+                                      const float* __restrict__ conv_bias, float eps, int C,
+                                      float* __restrict__ scale, float* __restrict__ shift) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float sc = gamma[c] * rsqrtf(var[c] + eps);
+  const float cb = conv_bias != nullptr ? conv_bias[c] : 0.f;
+  scale[c] = sc;
+  shift[c] = beta[c] + (cb - mean[c]) * sc;
+}
+
+void bn_fold_affine(const float* gamma, const float* beta, const float* mean, const float* var,
+                    const float* conv_bias, float eps, int C, float* scale, float* shift,
+                    hipStream_t st) {
+  hipLaunchKernelGGL(bn_fold_affine_kernel, dim3((C + 255) / 256), dim3(256), 0, st, gamma, beta,
+                     mean, var, conv_bias, eps, C, scale, shift);
+}
+
 // ----------------------------------------------------------------------------- forward apply
 // Each block owns a contiguous tile of kApplyU * rpb rows; a thread issues the loads of its
 // kApplyU rows before any arithmetic (two 16-B loads per stream in flight instead of one).

@@ -455,6 +455,7 @@ inline void with_tile(int cfg, F&& f) {
 
 // Heuristic tile choice when the tuning table has no entry (measured round-1 rules).
 int default_fwd_cfg(const ConvShape& s);
+int resolve_fwd_cfg(const ConvShape& s, int cfg);  // a plan's tile id if valid for the dtype, else the heuristic
 int default_dgrad_cfg(const ConvShape& s, long K_class);
 int default_wgrad_cfg(const ConvShape& s);
 

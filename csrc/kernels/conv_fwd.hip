@@ -18,7 +18,7 @@ int default_fwd_cfg(const ConvShape& s) {
   return ns1 ? 1 : 0;
 }
 
-static int resolve_fwd_cfg(const ConvShape& s, int cfg) {
+int resolve_fwd_cfg(const ConvShape& s, int cfg) {
   cfg = conv_plan_tile(cfg);
   const bool ok = s.f32 ? tile_ok_for<float>(cfg) : tile_ok_for<__bf16>(cfg);
   return ok ? cfg : default_fwd_cfg(s);
@@ -119,6 +119,50 @@ static void conv_fwd_t(const void* x, const void* w, void* y, float* st_sum, flo
     else
       hipLaunchKernelGGL((conv_fwd_kernel<C, false, false, T>), grid, block, 0, st, xp, wp, g, M, tN, ee);
   });
+}
+
+// The partial-tile launch of a split-K plan alone (conv_infer.hip runs its own finish kernel on
+// the workspace): the split kernels, grid and slice layout conv_fwd_t launches for the plan.
+template <class T>
+static int conv_fwd_split_partials_t(const void* x, const void* w, const ConvShape& s,
+                                     hipStream_t st, int cfg, float* split_ws) {
+  const int nk = (int)cdiv((uint64_t)s.KH * s.KW * s.Ci, BK);
+  int S, kps;
+  conv_split_geometry(nk, conv_plan_splits(cfg), &S, &kps);
+  if (S <= 1) return 1;
+  ConvGeom g = make_geom(s);
+  const uint32_t M = (uint32_t)s.N * s.Ho * s.Wo;
+  const bool dense = is_dense(s);
+  const bool aligned = s.Ci % BK == 0 && (s.f32 || s.KH * s.KW <= 32);
+  const T* xp = (const T*)x;
+  const T* wp = (const T*)w;
+  int launched = 1;
+  with_tile<T>(resolve_fwd_cfg(s, cfg), [&](auto tile) {
+    typedef decltype(tile) C;
+    constexpr bool kSplitOk = !(C::BM == 256 && C::BN == 256 && !C::PP);
+    if constexpr (kSplitOk) {
+      const uint32_t tN = cdiv(s.Co, C::BN), tiles = cdiv(M, C::BM) * tN;
+      EpiParams e{};
+      e.M = M; e.N = s.Co; e.fl_tiles = tiles;
+      e.split_kt = kps;
+      e.split_ws = split_ws;
+      const dim3 grid(tiles, S), block(C::THREADS);
+      if (dense)
+        hipLaunchKernelGGL((conv_fwd_kernel<C, true, false, T, false, true>), grid, block, 0, st, xp, wp, g, M, tN, e);
+      else if (aligned)
+        hipLaunchKernelGGL((conv_fwd_kernel<C, false, true, T, false, true>), grid, block, 0, st, xp, wp, g, M, tN, e);
+      else
+        hipLaunchKernelGGL((conv_fwd_kernel<C, false, false, T, false, true>), grid, block, 0, st, xp, wp, g, M, tN, e);
+      launched = S;
+    }
+  });
+  return launched;
+}
+
+int conv_fwd_split_partials(const void* x, const void* w, const ConvShape& s, hipStream_t st,
+                            int cfg, float* split_ws) {
+  return s.f32 ? conv_fwd_split_partials_t<float>(x, w, s, st, cfg, split_ws)
+               : conv_fwd_split_partials_t<__bf16>(x, w, s, st, cfg, split_ws);
 }
 
 void conv_fwd(const void* x, const void* w, void* y, float* st_sum, float* st_sq,

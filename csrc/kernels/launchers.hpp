@@ -76,6 +76,17 @@ void conv_fwd(const void* x, const void* w, void* y, float* st_sum, float* st_sq
               const float* bias = nullptr, bool relu = false, int cfg = -1, int det_rows = 0,
               void* wflip = nullptr, float* split_ws = nullptr,
               const float* in_scale = nullptr, const float* in_bias = nullptr);
+// Inference forward (conv_infer.hip): y = act(conv(x, w) * scale + shift + residual) in one
+// launch (plus the split launch of a split-K plan).  scale / shift: fp32 [Co] or null (1 / 0),
+// 16-B aligned; residual: y's dtype and shape, contiguous, not y itself, or null.  cfg and
+// split_ws as conv_fwd.
+void conv_fwd_infer(const void* x, const void* w, void* y, const ConvShape& s, hipStream_t st,
+                    const float* scale, const float* shift, const void* residual, bool relu,
+                    int cfg = -1, float* split_ws = nullptr);
+// the partial-tile launch of a split-K forward plan alone; returns the number of slices written
+// (1: the plan does not split, nothing was launched)
+int conv_fwd_split_partials(const void* x, const void* w, const ConvShape& s, hipStream_t st,
+                            int cfg, float* split_ws);
 constexpr int kConvBnInMaxK = 1024;  // input channels of a folded-BN forward (LDS table)
 inline bool conv_is_dense(const ConvShape& s) {  // 1x1, stride 1, no padding
   return s.KH == 1 && s.KW == 1 && s.stride == 1 && s.pad == 0 && s.pad_w <= 0 &&
@@ -275,6 +286,11 @@ void bn_finalize(float* psum, float* psq, int P, int C, long count, const float*
                  const float* gamma, const float* beta, float* run_mean, float* run_var,
                  float momentum, float eps, float* mean, float* invstd, float* scale, float* bias,
                  bool zero_after, long long* nbt, hipStream_t st);
+// Eval-mode BatchNorm as a per-channel affine, one launch: scale = gamma * rsqrt(var + eps),
+// shift = beta + (conv_bias - mean) * scale  (conv_bias may be null: 0)
+void bn_fold_affine(const float* gamma, const float* beta, const float* mean, const float* var,
+                    const float* conv_bias, float eps, int C, float* scale, float* shift,
+                    hipStream_t st);
 // z = act(y*scale + bias [+ r | + r*rscale + rbias])   (M rows of C channels, bf16 or f32)
 void bn_act_fwd(const void* y, const float* scale, const float* bias, const void* r,
                 const float* rscale, const float* rbias, void* z, long M, int C, bool relu,

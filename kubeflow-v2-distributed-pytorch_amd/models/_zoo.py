@@ -52,6 +52,10 @@ def conv_bn(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, act: str = 
     MFMA epilogue and BN (+residual) (+ReLU) is one elementwise pass; other convs run the
     direct kernel, then the any-C BN pass."""
     cin = x.shape[-1]
+    if conv.dense(cin) and act in ("none", "relu") and mnn.fused_eval_applies(bn):
+        # fused evaluation: BN (+ conv bias) (+ residual) (+ ReLU) in the conv's epilogue
+        return mnn.fused_eval_conv_bn(x, conv.kernel_weight(x.dtype, cin), conv.bias, bn,
+                                      conv.stride[0], conv.mfma_pad(), act == "relu", residual)
     if conv.dense(cin) and conv.bias is None and act in ("none", "relu"):
         w_c = conv.kernel_weight(x.dtype, cin)
         s, p = conv.stride[0], conv.mfma_pad()

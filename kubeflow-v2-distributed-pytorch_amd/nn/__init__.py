@@ -21,9 +21,11 @@ import torch.nn as tnn
 
 from mipipe.ops import functional as MF
 from mipipe.ops import kernels as K
+from mipipe.ops.inference import is_fused_eval
 
 __all__ = ["Conv2d", "BatchNorm2d", "Linear", "ReLU", "MaxPool2d", "AdaptiveAvgPool2d",
-           "Embedding", "LayerNorm", "Dropout", "ShadowMixin", "conv_bn_act", "XConv2d"]
+           "Embedding", "LayerNorm", "Dropout", "ShadowMixin", "conv_bn_act", "XConv2d", "fused_eval_applies",
+           "fused_eval_conv_bn"]
 
 
 class ShadowMixin:
@@ -205,6 +207,39 @@ def _foldable_into_1x1(y: torch.Tensor) -> bool:
     return _BN_FOLD_MODE == "1" or y.numel() >= _BN_FOLD_MIN
 
 
+def fused_eval_applies(bn: tnn.BatchNorm2d) -> bool:
+    """The fused evaluation path (:mod:`mipipe.ops.inference`) may replace conv -> ``bn``: the
+    switch is on, the BN normalises with its running statistics and nothing records a graph."""
+    return (is_fused_eval() and not bn.training and not torch.is_grad_enabled()
+            and bn.running_var is not None and bn.weight is not None)
+
+
+def fused_eval_conv_bn(x: torch.Tensor, w_c: torch.Tensor, conv_bias: Optional[torch.Tensor],
+                       bn: tnn.BatchNorm2d, stride, pad, relu: bool,
+                       residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(BN_eval(conv(x, w_c) + conv_bias) [+ residual]): one small launch folds the BN (and
+    the bias) into a per-channel affine — every forward: the optimizer and ``bn_finalize`` update
+    the parameters and running statistics behind the tensors' version counters, so a cached fold
+    could be stale — and the conv applies it, the residual and the ReLU in its epilogue."""
+    scale, shift = K.bn_fold_affine(bn.weight.detach(), bn.bias.detach(), bn.running_mean,
+                                    bn.running_var, bn.eps,
+                                    None if conv_bias is None else conv_bias.detach())
+    if residual is not None:
+        residual = residual.contiguous()
+    return MF.conv_affine_act(x, w_c, scale, shift, stride, pad, relu, residual)
+
+
+def _fused_eval_ok(conv, bn) -> bool:
+    # (a conv with its own forward — the packed stem — keeps its path)
+    return (fused_eval_applies(bn) and isinstance(conv, Conv2d)
+            and type(conv).forward is Conv2d.forward)
+
+
+def _fused_eval_conv(x, conv: Conv2d, bn, relu: bool, residual=None) -> torch.Tensor:
+    return fused_eval_conv_bn(x, conv.compute_weight(x.dtype), conv.bias, bn, conv.stride[0],
+                              conv.padding[0], relu, residual)
+
+
 def conv_bn_act(x: torch.Tensor, conv: Conv2d, bn: BatchNorm2d, relu: bool = True,
                 residual: Optional[torch.Tensor] = None,
                 branch: Optional[tuple] = None, fuse_prev: bool = False,
@@ -225,7 +260,15 @@ def conv_bn_act(x: torch.Tensor, conv: Conv2d, bn: BatchNorm2d, relu: bool = Tru
     transform their operand fragments (gemm_core.hpp KCDenseBufBN / MCDenseBufBN), so the
     normalised activation is never written (saves a read and a write of the tensor per step; large
     tensors only by default, see _BN_FOLD_MODE).  The returned tensor is then an alias of y.
+
+    Fused evaluation (:mod:`mipipe.ops.inference`, eval mode under ``no_grad``): the whole group
+    is one inference-conv launch; a downsample branch runs first, fused with its own BN, and its
+    output is the main conv's residual.  No tokens are attached: there is no backward.
     """
+    if _fused_eval_ok(conv, bn) and (branch is None or _fused_eval_ok(branch[1], branch[2])):
+        if branch is not None:
+            residual = _fused_eval_conv(branch[0], branch[1], branch[2], False)
+        return _fused_eval_conv(x, conv, bn, relu, residual)
     use_batch = bn.training
     prev = getattr(x, "_mipipe_bnact", None) if fuse_prev else None
     in_bn = getattr(x, "_mipipe_lazy_bn", None) if fuse_prev else None

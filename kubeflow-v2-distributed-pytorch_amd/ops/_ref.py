@@ -51,6 +51,33 @@ def conv_fwd(x: Tensor, w: Tensor, stride: int, pad: int,
     return y.to(x.dtype), d.sum(0, keepdim=True), (d * d).sum(0, keepdim=True)
 
 
+def conv_fwd_infer(x: Tensor, w: Tensor, stride, pad, scale: Optional[Tensor] = None,
+                   shift: Optional[Tensor] = None, residual: Optional[Tensor] = None,
+                   relu: bool = False) -> Tensor:
+    """Inference forward (csrc/kernels/conv_infer.hip's contract), NHWC:
+    ``act(conv(x, w) * scale[c] + shift[c] + residual)`` in fp32 (float64 for float64 inputs),
+    rounded once to ``x``'s dtype.  ``scale`` / ``shift`` absent = 1 / 0."""
+    y = _nhwc(F.conv2d(_f(_nchw(x)), _f(_w_oihw(w)), stride=stride, padding=pad))
+    if scale is not None:
+        y = y * scale.to(y.dtype)
+    if shift is not None:
+        y = y + shift.to(y.dtype)
+    if residual is not None:
+        y = y + residual.to(y.dtype)
+    if relu:
+        y = torch.relu(y)
+    return y.to(x.dtype)
+
+
+def bn_fold_affine(weight: Tensor, bias: Tensor, running_mean: Tensor, running_var: Tensor,
+                   eps: float, conv_bias: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Eval-mode BatchNorm of ``conv + conv_bias`` as a per-channel affine:
+    ``scale = γ·rsqrt(var + eps)``, ``shift = β + (conv_bias − mean)·scale``."""
+    scale = _f(weight) * torch.rsqrt(_f(running_var) + eps)
+    d = -_f(running_mean) if conv_bias is None else _f(conv_bias) - _f(running_mean)
+    return scale, _f(bias) + d * scale
+
+
 def conv_dgrad(dy: Tensor, w: Tensor, x_shape, stride: int, pad: int) -> Tensor:
     N, H, W, Ci = x_shape
     dx = torch.nn.grad.conv2d_input((N, Ci, H, W), _f(_w_oihw(w)), _f(_nchw(dy)),

@@ -428,6 +428,18 @@ def conv2d_bias_act(x: Tensor, weight: Tensor, w_c: Tensor, bias: Optional[Tenso
     return _ConvBiasActFn.apply(x, weight, w_c, bias, stride, pad, relu)
 
 
+def conv_affine_act(x: Tensor, w_c: Tensor, scale: Optional[Tensor], shift: Optional[Tensor],
+                    stride, pad, relu: bool, residual: Optional[Tensor] = None) -> Tensor:
+    """Inference only: ``act(conv(x, w_c) * scale + shift [+ residual])`` in one conv launch
+    (:func:`mipipe.ops.kernels.conv_fwd_infer`).  There is no autograd node: calling it where a
+    gradient would be needed is an error, not a silently detached result."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                       for t in (x, w_c, scale, shift, residual)):
+        raise RuntimeError("conv_affine_act is inference only: call it under torch.no_grad() "
+                           "(or on inputs that do not require grad)")
+    return K.conv_fwd_infer(x, w_c, stride, pad, scale, shift, residual, relu)
+
+
 class _GConvFn(Function):
     """Grouped / depthwise / non-square / odd-channel convolution (+bias, +activation) on the
     direct NHWC kernels of vision.hip.  The activation's mask is recomputed from the saved

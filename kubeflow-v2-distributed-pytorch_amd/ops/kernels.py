@@ -15,7 +15,7 @@ from . import _ref
 from ._ref import _f
 from ._native import native, native_available
 
-__all__ = ["conv_fwd", "conv_dgrad", "conv_wgrad", "bn_finalize", "bn_act_fwd",
+__all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_wgrad", "bn_finalize", "bn_act_fwd",
            "bn_act_bwd_reduce", "bn_act_bwd_apply", "maxpool_fwd", "maxpool_bwd",
            "avgpool_fwd", "avgpool_bwd", "pool_bn_fwd", "pool_bn_bwd", "pool_bn_supported", "stem_fused_supported", "stem_fwd_stats",
            "stem_fwd_pool", "stem_bwd", "gemm", "cross_entropy_fwd_bwd", "top1_correct", "sgd_step",
@@ -70,6 +70,28 @@ def conv_fwd(x, w, stride, pad, stats_shift=None, slabs=None, bias=None, relu=Fa
         yf = _f(y) if bias is None else _f(y) + _f(bias)
         y = (torch.relu(yf) if relu else yf).to(x.dtype)
     return y, a, b
+
+
+def conv_fwd_infer(x, w, stride, pad, scale=None, shift=None, residual=None, relu=False):
+    """Inference forward: ``act(conv(x, w) * scale + shift + residual)`` in the conv's epilogue
+    (one launch; ``scale`` / ``shift`` fp32 [Co] from :func:`bn_fold_affine`, ``residual`` of the
+    output's dtype and shape).  No statistics, no backward."""
+    if use_native(x):
+        sh, sw = (stride, 0) if isinstance(stride, int) else (stride[0], stride[1])
+        ph, pw = _pads(pad)
+        return native().conv_fwd_infer(x, w, sh, ph, scale, shift, residual, relu, sw, pw)
+    return _ref.conv_fwd_infer(x, w, stride if isinstance(stride, int) else tuple(stride),
+                               pad if isinstance(pad, int) else tuple(pad), scale, shift,
+                               residual, relu)
+
+
+def bn_fold_affine(weight, bias, running_mean, running_var, eps, conv_bias=None):
+    """(scale, shift) of an eval-mode BatchNorm applied to ``conv + conv_bias``: one launch.
+    Never cached: the optimizer and ``bn_finalize`` write parameters and running statistics
+    through raw pointers, so tensor versions do not say whether they changed."""
+    if use_native(weight):
+        return native().bn_fold_affine(weight, bias, running_mean, running_var, eps, conv_bias)
+    return _ref.bn_fold_affine(weight, bias, running_mean, running_var, eps, conv_bias)
 
 
 def dgrad_preflip_ok(x_shape, w_shape, stride, pad) -> bool:

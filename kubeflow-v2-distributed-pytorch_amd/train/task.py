@@ -48,6 +48,7 @@ from mipipe.parallel import dist_utils
 from mipipe.data.synthetic import DATASET_SHAPES, DeviceBatchLoader, SyntheticImageDataset
 from mipipe.optim import SGD
 from mipipe.ops import functional as MF
+from mipipe.ops import inference
 from mipipe.train import checkpoint as ckpt
 from mipipe.obs.meter import ThroughputMeter
 
@@ -202,6 +203,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="allow float-atomic reductions (faster)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"],
                    help="compute dtype on GPU (master weights stay fp32); CPU runs fp32")
+    p.add_argument("--fused-eval", type=int, choices=[0, 1], default=0,
+                   help="evaluate with BatchNorm, residual and ReLU fused into the conv epilogues "
+                        "(mipipe.ops.inference; MIPIPE_FUSED_EVAL=1 turns it on as well)")
     p.add_argument("--hip-graph", action="store_true",
                    help="replay full-size training steps (forward, backward with the DDP bucket "
                         "all-reduces, SGD) from one captured hipGraph; partial batches run eagerly")
@@ -461,12 +465,14 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         optimizer.step()
         return loss_
 
+    fused = bool(args.fused_eval) or inference.is_fused_eval()
     for epoch in range(start_epoch, args.num_epochs):
         epoch_start = datetime.now().strftime("%Y_%m_%d_%H_%M_%S")
         print(f"Rank: {args.rank}, Epoch: {epoch}, Training start: {epoch_start}", flush=True)
         train_sampler.set_epoch(epoch)
         if epoch % args.eval_every == 0:
-            accuracy = evaluate(model, device, test_loader)
+            with inference.fused_eval(fused):
+                accuracy = evaluate(model, device, test_loader)
             if args.rank == 0:
                 ckpt.export_model(model, args, epoch, accuracy)
                 print("-" * 75)
@@ -521,7 +527,8 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
     if isinstance(model, DistributedDataParallel):
         model.check_comm_errors(final=True)
     # fixed quirk: evaluate and save the *trained* model at the end as well
-    accuracy = evaluate(model, device, test_loader)
+    with inference.fused_eval(fused):
+        accuracy = evaluate(model, device, test_loader)
     best_acc1 = max(best_acc1, accuracy)
     last_loss = float(loss.detach().float().item()) if global_step else last_loss
     metrics = {"accuracy": accuracy, "loss": last_loss, "epochs": args.num_epochs,
@@ -531,7 +538,8 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                "samples_per_sec_job": meter.samples_per_sec() * world,
                "dtype": str(compute_dtype).replace("torch.", ""), "device": str(device),
                "backend": (torch.distributed.get_backend() if args.distributed else "none"),
-               "hip_graph": bool(args.hip_graph), "deterministic": bool(args.deterministic)}
+               "hip_graph": bool(args.hip_graph), "deterministic": bool(args.deterministic),
+               "fused_eval": fused}
     if args.rank == 0:
         ckpt.export_model(model, args, args.num_epochs, accuracy)
         ckpt.save_checkpoint(model, optimizer, args, args.num_epochs, best_acc1)
