@@ -1517,6 +1517,123 @@ void adamw_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> shadow,
                      i32_dev(step_dev, "step_dev"));
 }
 
+// ---- LARS / LAMB (csrc/kernels/optim.hip): the optimizer's device tables, checked per call
+struct OptimTabs {
+  const int *chunks, *segs;
+  int nchunks, nseg;
+  float *part, *segtot, *ratio, *scal;
+  const int* t_dev;
+};
+static OptimTabs optim_tabs(const Tensor& chunks, const Tensor& segs, const Tensor& part,
+                            const Tensor& segtot, const Tensor& ratio, const Tensor& scal,
+                            const Tensor& t_dev) {
+  auto i4 = [](const Tensor& t, const char* name) {
+    check_cuda(t, name);
+    TORCH_CHECK(t.scalar_type() == at::kInt && t.dim() == 2 && t.size(1) == 4, name,
+                " must be int32 [n, 4]");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-B aligned");
+  };
+  i4(chunks, "chunks");
+  i4(segs, "segs");
+  OptimTabs o;
+  o.nchunks = (int)chunks.size(0);
+  o.nseg = (int)segs.size(0);
+  TORCH_CHECK(o.nseg >= 1 && o.nchunks >= o.nseg, "optimizer tables: every segment has a chunk");
+  check_vec(part, 2 * (int64_t)o.nchunks, "part");
+  check_vec(segtot, 2 * (int64_t)o.nseg, "segtot");
+  check_vec(ratio, o.nseg, "ratio");
+  check_vec(scal, 4, "scal");
+  check_cuda(t_dev, "step_dev");
+  TORCH_CHECK(t_dev.scalar_type() == at::kInt && t_dev.numel() == 1, "step_dev must be int32 [1]");
+  o.chunks = chunks.data_ptr<int>();
+  o.segs = segs.data_ptr<int>();
+  o.part = part.data_ptr<float>();
+  o.segtot = segtot.data_ptr<float>();
+  o.ratio = ratio.data_ptr<float>();
+  o.scal = scal.data_ptr<float>();
+  o.t_dev = t_dev.data_ptr<int>();
+  return o;
+}
+
+static void* optim_shadow(const optional<Tensor>& shadow, int64_t n) {
+  if (!shadow.has_value()) return nullptr;
+  check_cuda(*shadow, "shadow");
+  TORCH_CHECK(shadow->numel() == n && shadow->scalar_type() == at::kBFloat16, "shadow mismatch");
+  return shadow->data_ptr();
+}
+
+static mipipe::OptimSched optim_sched(int64_t kind, double base, double end, int64_t warmup,
+                                      int64_t total) {
+  TORCH_CHECK(kind >= 0 && kind <= 3, "schedule kind must be 0..3");
+  TORCH_CHECK(warmup >= 0 && total >= 0 && warmup < (1ll << 31) && total < (1ll << 31),
+              "schedule steps out of range");
+  return mipipe::OptimSched{(int)kind, (float)base, (float)end, (int)warmup, (int)total};
+}
+
+// One LARS step (3 launches; 2 when neither the trust ratio nor clipping needs the norms).
+// tc < 0: no trust ratio.  max_norm <= 0: no clipping.
+void lars_step(Tensor p, Tensor g, Tensor m, optional<Tensor> shadow, Tensor chunks, Tensor segs,
+               Tensor part, Tensor segtot, Tensor ratio, Tensor scal, Tensor step_dev,
+               double momentum, double tc, double eps, double max_norm, double grad_scale,
+               int64_t kind, double base_lr, double end_lr, int64_t warmup, int64_t total) {
+  const int64_t n = p.numel();
+  TORCH_CHECK(n % 64 == 0, "flat buffer size must be a multiple of 64");
+  check_flat(p, n, "param");
+  check_flat(g, n, "grad");
+  check_flat(m, n, "momentum");
+  c10::DeviceGuard gd(p.device());
+  void* sh = optim_shadow(shadow, n);
+  const OptimTabs t = optim_tabs(chunks, segs, part, segtot, ratio, scal, step_dev);
+  const auto sc = optim_sched(kind, base_lr, end_lr, warmup, total);
+  const bool norms = tc >= 0 || max_norm > 0;
+  if (norms)
+    mipipe::optim_seg_sumsq(p.data_ptr<float>(), g.data_ptr<float>(), t.chunks, t.nchunks, t.nseg,
+                            n, (float)grad_scale, true, t.part, stream());
+  mipipe::optim_seg_finish(t.part, t.nchunks, t.segs, t.nseg, t.segtot, t.ratio, t.scal, t.t_dev,
+                           norms ? 0 : 3, (float)tc, (float)eps, (float)max_norm, sc, stream());
+  mipipe::optim_lars_apply(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), sh,
+                           t.chunks, t.segs, t.nchunks, t.nseg, n, (float)grad_scale,
+                           (float)momentum, t.ratio, t.scal, stream());
+}
+
+// One LAMB step: moments, finish, apply; with max_norm > 0 a gradient-norm pass and its finish
+// come first (5 launches).
+void lamb_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> shadow, Tensor chunks,
+               Tensor segs, Tensor part, Tensor segtot, Tensor ratio, Tensor scal,
+               Tensor step_dev, double b1, double b2, double eps, double max_norm,
+               double grad_scale, int64_t kind, double base_lr, double end_lr, int64_t warmup,
+               int64_t total) {
+  const int64_t n = p.numel();
+  TORCH_CHECK(n % 64 == 0, "flat buffer size must be a multiple of 64");
+  TORCH_CHECK(b1 > 0 && b1 < 1 && b2 > 0 && b2 < 1, "LAMB betas must lie in (0, 1)");
+  check_flat(p, n, "param");
+  check_flat(g, n, "grad");
+  check_flat(m, n, "exp_avg");
+  check_flat(v, n, "exp_avg_sq");
+  c10::DeviceGuard gd(p.device());
+  void* sh = optim_shadow(shadow, n);
+  const OptimTabs t = optim_tabs(chunks, segs, part, segtot, ratio, scal, step_dev);
+  const auto sc = optim_sched(kind, base_lr, end_lr, warmup, total);
+  float *pp = p.data_ptr<float>(), *gp = g.data_ptr<float>();
+  float *mp = m.data_ptr<float>(), *vp = v.data_ptr<float>();
+  const float lnb1 = (float)std::log(b1), lnb2 = (float)std::log(b2);
+  if (max_norm > 0) {
+    mipipe::optim_seg_sumsq(pp, gp, t.chunks, t.nchunks, t.nseg, n, (float)grad_scale, false,
+                            t.part, stream());
+    mipipe::optim_seg_finish(t.part, t.nchunks, t.segs, t.nseg, t.segtot, t.ratio, t.scal, t.t_dev,
+                             1, 0.f, 0.f, (float)max_norm, sc, stream());
+  }
+  mipipe::optim_lamb_moments(pp, gp, mp, vp, t.chunks, t.segs, t.nchunks, t.nseg, n,
+                             (float)grad_scale, (float)b1, (float)(1.0 - b1), (float)b2,
+                             (float)(1.0 - b2), lnb1, lnb2, (float)eps,
+                             max_norm > 0 ? t.scal : nullptr, t.t_dev, t.part,
+                             stream());
+  mipipe::optim_seg_finish(t.part, t.nchunks, t.segs, t.nseg, t.segtot, t.ratio, t.scal, t.t_dev, 2,
+                           0.f, 0.f, 0.f, sc, stream());
+  mipipe::optim_lamb_apply(pp, mp, vp, sh, t.chunks, t.segs, t.nchunks, t.nseg, n, lnb1, lnb2,
+                           (float)eps, t.ratio, t.scal, t.t_dev, stream());
+}
+
 Tensor nchw_to_nhwc(Tensor x, at::ScalarType dtype, int64_t pad_to) {
   check_cuda(x, "x");
   c10::DeviceGuard g(x.device());
@@ -2303,6 +2420,18 @@ PYBIND11_MODULE(_C, m) {
   m.def("adamw_step", &adamw_step, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"),
         py::arg("shadow"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
         py::arg("wd"), py::arg("step"), py::arg("grad_scale"), py::arg("step_dev") = py::none());
+  m.def("lars_step", &lars_step, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("shadow"),
+        py::arg("chunks"), py::arg("segs"), py::arg("part"), py::arg("segtot"), py::arg("ratio"),
+        py::arg("scal"), py::arg("step_dev"), py::arg("momentum"), py::arg("tc"), py::arg("eps"),
+        py::arg("max_norm"), py::arg("grad_scale"), py::arg("kind"), py::arg("base_lr"),
+        py::arg("end_lr"), py::arg("warmup"), py::arg("total"));
+  m.def("lamb_step", &lamb_step, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"),
+        py::arg("shadow"), py::arg("chunks"), py::arg("segs"), py::arg("part"),
+        py::arg("segtot"), py::arg("ratio"), py::arg("scal"), py::arg("step_dev"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("max_norm"), py::arg("grad_scale"),
+        py::arg("kind"), py::arg("base_lr"), py::arg("end_lr"), py::arg("warmup"),
+        py::arg("total"));
+  m.attr("OPTIM_CHUNK") = mipipe::kOptimChunk;
   m.def("nchw_to_nhwc", &nchw_to_nhwc);
   m.def("synthetic_batch", &synthetic_batch);
   m.def("record_decode", &record_decode, py::arg("rec"), py::arg("idx"), py::arg("affine"),

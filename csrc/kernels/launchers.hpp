@@ -381,6 +381,40 @@ void grad_unpack_bf16(const void* wire, float* g, long n, hipStream_t st);
 void adamw_step(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr,
                 float b1, float b2, float eps, float wd, float bc1, float bc2, float grad_scale,
                 hipStream_t st, const int* t_dev = nullptr);
+// LARS / LAMB over the flat buffer (csrc/kernels/optim.hip).  chunks: int32 [nchunks][4] =
+// {segment, offset / 64, length, 0}, length <= kOptimChunk, offset and length multiples of 64, no
+// chunk crossing a segment; segs: int32 [nseg][4] = {weight decay (float bits), adapt flag, first
+// chunk, chunk count}; part: [2][nchunks] partial sums of squares; segtot: [2][nseg] scratch;
+// ratio: [nseg] trust ratios; scal: {lr, clip, gradient norm, -}; t_dev: the device step count
+// (already advanced: the step being taken is t - 1).  Every per-step value is device memory.
+constexpr int kOptimChunk = 8192;
+struct OptimSched {  // LR schedule: kind 0 constant, 1 linear, 2 poly (power 2), 3 cosine
+  int kind;
+  float base, end;
+  int warmup, total;
+};
+// part[0] = sum w^2 per chunk (with_w, else 0), part[1] = sum (g * grad_scale)^2
+void optim_seg_sumsq(const float* p, const float* g, const int* chunks, int nchunks, int nseg,
+                     long n, float grad_scale, bool with_w, float* part, hipStream_t st);
+// m, v updated in place from g * grad_scale * scal[1] (scal null: no clipping); part[0] =
+// sum w^2, part[1] = sum u^2
+void optim_lamb_moments(const float* p, const float* g, float* m, float* v, const int* chunks,
+                        const int* segs, int nchunks, int nseg, long n, float grad_scale,
+                        float b1, float omb1, float b2, float omb2, float lnb1, float lnb2,
+                        float eps, const float* scal, const int* t_dev, float* part,
+                        hipStream_t st);
+// mode 0 LARS (norm, clip, ratios, lr), 1 clip only (norm, clip, lr), 2 LAMB (ratios, lr),
+// 3 lr only (ratios = clip = 1; part is not read)
+void optim_seg_finish(const float* part, int nchunks, const int* segs, int nseg, float* segtot,
+                      float* ratio, float* scal, const int* t_dev, int mode, float tc, float eps,
+                      float max_norm, const OptimSched& sched, hipStream_t st);
+void optim_lars_apply(float* p, const float* g, float* m, void* shadow, const int* chunks,
+                      const int* segs, int nchunks, int nseg, long n, float grad_scale,
+                      float momentum, const float* ratio, const float* scal, hipStream_t st);
+void optim_lamb_apply(float* p, const float* m, const float* v, void* shadow, const int* chunks,
+                      const int* segs, int nchunks, int nseg, long n, float lnb1, float lnb2,
+                      float eps, const float* ratio, const float* scal, const int* t_dev,
+                      hipStream_t st);
 void nchw_to_nhwc(const void* x, bool x_is_bf16, void* y, int N, int C, int H, int W, int Cp,
                   hipStream_t st, bool y_f32 = false);
 // Stem "super-pixel" packing (C <= 4): y[n][h'][j][p*4 + c] = x[n][c][h'-pad][2j+p-pad] (zero

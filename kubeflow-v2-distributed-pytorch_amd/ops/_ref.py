@@ -265,6 +265,78 @@ def adamw_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
         shadow.copy_(param.to(shadow.dtype))
 
 
+# ---- large-batch optimizers: the contract of csrc/kernels/optim.hip, written per tensor (no flat
+# layout, no chunks) and in the tensors' own dtype, so the same code is the fp32 CPU path and,
+# given float64 tensors, the oracle of the GPU tests.
+
+def lr_schedule(kind: str, base_lr: float, warmup_steps: int, total_steps: int, end_lr: float,
+                k: int) -> float:
+    """Learning rate of step ``k`` (from 0), in double precision: ``base·(k+1)/W`` for ``k < W``,
+    then from ``base`` to ``end`` over ``x = (k−W)/(T−W)`` clamped to [0, 1]."""
+    W, T = int(warmup_steps), int(total_steps)
+    if k < W:
+        return base_lr * (k + 1) / W
+    if kind == "constant":
+        return base_lr
+    x = min(1.0, (k - W) / (T - W)) if T > W else 1.0
+    if kind == "linear":
+        f = 1.0 - x
+    elif kind == "poly":
+        f = (1.0 - x) ** 2
+    elif kind == "cosine":
+        f = 0.5 * (1.0 + math.cos(math.pi * x))
+    else:
+        raise ValueError(f"unknown LR schedule '{kind}'")
+    return end_lr + (base_lr - end_lr) * f
+
+
+def clip_coef(grads, grad_scale: float = 1.0, max_norm: Optional[float] = None):
+    """(‖g·grad_scale‖ over all tensors, clip) with torch.nn.utils.clip_grad_norm_'s rule
+    ``clip = min(1, max_norm / (norm + 1e-6))``; ``max_norm=None``: clip = 1."""
+    tot = sum(((g * grad_scale) ** 2).sum() for g in grads)
+    norm = torch.sqrt(tot)
+    if max_norm is None:
+        return norm, torch.ones_like(norm)
+    return norm, torch.clamp(max_norm / (norm + 1e-6), max=1.0)
+
+
+def lars_step(w: Tensor, g: Tensor, m: Tensor, lr: float, momentum: float, weight_decay: float,
+              trust_coefficient: Optional[float], eps: float, adapt: bool,
+              grad_scale=1.0) -> Tensor:
+    """One tensor's LARS update in place (LARC-style composition); returns the trust ratio.
+    ``g' = g·grad_scale`` (``grad_scale`` already holds the clip coefficient);
+    ``r = tc·‖w‖ / (‖g'‖ + wd·‖w‖ + eps)`` if adapted and both norms > 0, else 1;
+    ``d = r·(g' + wd·w)``; ``m = μ·m + d``; ``w −= lr·m``.  With r = 1 this is plain SGD."""
+    gp = g * grad_scale
+    r = torch.ones((), dtype=w.dtype, device=w.device)
+    if adapt and trust_coefficient is not None:
+        wn, gn = w.norm(), gp.norm()
+        if wn > 0 and gn > 0:
+            r = trust_coefficient * wn / (gn + weight_decay * wn + eps)
+    d = r * (gp + weight_decay * w)
+    m.mul_(momentum).add_(d)
+    w.sub_(lr * m)
+    return r
+
+
+def lamb_step(w: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: float, beta2: float,
+              eps: float, weight_decay: float, step: int, adapt: bool, grad_scale=1.0) -> Tensor:
+    """One tensor's LAMB update in place; returns the trust ratio.  ``step`` counts from 1.
+    ``u = (m/(1−β1ᵗ)) / (√(v/(1−β2ᵗ)) + eps) + wd·w``; ``r = ‖w‖/‖u‖`` if adapted and both
+    norms > 0, else 1; ``w −= lr·r·u``."""
+    gp = g * grad_scale
+    m.mul_(beta1).add_(gp, alpha=1 - beta1)
+    v.mul_(beta2).addcmul_(gp, gp, value=1 - beta2)
+    u = (m / (1 - beta1 ** step)) / ((v / (1 - beta2 ** step)).sqrt() + eps) + weight_decay * w
+    r = torch.ones((), dtype=w.dtype, device=w.device)
+    if adapt:
+        wn, un = w.norm(), u.norm()
+        if wn > 0 and un > 0:
+            r = wn / un
+    w.sub_(lr * r * u)
+    return r
+
+
 def layernorm_fwd(x: Tensor, gamma: Tensor, beta: Tensor, eps: float,
                   residual: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
     """(y, mean, rstd, x_sum): y = LN(x [+ residual]); x_sum = x+residual (saved for bwd)."""

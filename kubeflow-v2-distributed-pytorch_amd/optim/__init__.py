@@ -10,6 +10,10 @@ Both run ONE HIP kernel over the model's flat fp32 parameter buffer
 (:class:`~mipipe.optim.flat.FlatParamSpace`) that also rewrites the bf16 compute shadow.
 ``state_dict()`` uses torch.optim's format (``{'state': {i: {'momentum_buffer': ..}},
 'param_groups': [...]}``) so checkpoints are interchangeable with torch.optim.SGD.
+
+``LARS`` / ``LAMB`` / ``LRSchedule`` (:mod:`mipipe.optim.large_batch`, ``csrc/kernels/optim.hip``)
+are the large-batch optimizers: layer-wise trust ratios, global-norm clipping and a learning-rate
+schedule whose per-step values all live on the device.
 """
 from __future__ import annotations
 
@@ -21,7 +25,8 @@ import torch
 from mipipe.ops import kernels as K
 from .flat import FlatParamSpace, get_flat_space, flat_space_for
 
-__all__ = ["SGD", "AdamW", "FlatParamSpace", "get_flat_space", "flat_space_for"]
+__all__ = ["SGD", "AdamW", "LARS", "LAMB", "LRSchedule", "FlatParamSpace", "get_flat_space",
+           "flat_space_for"]
 
 
 def _default_shadow_dtype(params: List[torch.Tensor]) -> Optional[torch.dtype]:
@@ -190,3 +195,8 @@ class AdamW(_FlatOptimizer):
         for p in self.params:
             self.state[p]["step"] = torch.tensor(float(self._step))
         return loss
+
+
+# large-batch training: LARS / LAMB with clipping and a device-side LR schedule (built on
+# _FlatOptimizer above, hence imported last)
+from .large_batch import LARS, LAMB, LRSchedule  # noqa: E402

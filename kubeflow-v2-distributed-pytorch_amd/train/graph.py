@@ -31,12 +31,17 @@ def graph_safe(model: torch.nn.Module, optimizer) -> Tuple[bool, str]:
     """Whether a step of ``model`` + ``optimizer`` can be replayed from one capture.
 
     Per-step values must live on the device: SGD has none; AdamW's step count / bias corrections
-    are a device counter (``device_step``); mipipe dropout seeds take their per-step part from a
+    are a device counter (``device_step``); LARS / LAMB keep step count, learning rate, clip
+    coefficient and trust ratios on the device; mipipe dropout seeds take their per-step part from a
     device counter when the model declares ``device_seeds`` (BERT on the GPU)."""
-    from mipipe.optim import SGD, AdamW
+    from mipipe.optim import SGD, AdamW, LARS, LAMB
     if isinstance(optimizer, AdamW):
         if not getattr(optimizer, "device_step", False):
             return False, "AdamW without a device step counter (CPU) uses host-side bias corrections"
+    elif isinstance(optimizer, (LARS, LAMB)):
+        # step count, LR, clip coefficient and trust ratios are device memory (optim/large_batch.py)
+        if not getattr(optimizer, "device_step", False):
+            return False, f"{type(optimizer).__name__} on the CPU computes its LR on the host"
     elif not isinstance(optimizer, SGD):
         return False, f"{type(optimizer).__name__} uses host-side per-step scalars"
     root = getattr(model, "module", model)

@@ -21,6 +21,18 @@ Deliberate fixes of reference quirks, each noted inline:
   * data is synthetic and generated on the GPU (no download race, no CPU decode).
 Additions: ``--dtype``, ``--dataset``, ``--steps``, ``--bench``, ``--num_classes``,
 ``--eval-every``, metrics JSON with samples/sec, fault injection for tests.
+
+Large-batch training (``mipipe.optim.LARS`` / ``LAMB``; all of it stays on under ``--hip-graph``,
+the per-step values being device memory):
+  * ``--optimizer {sgd,lars,lamb}`` (default ``sgd``: the reference's SGD, unchanged);
+  * ``--lr-schedule {constant,linear,poly,cosine}`` with ``--lr-warmup-steps`` and
+    ``--lr-total-steps`` (default ``num_epochs`` x steps per epoch): linear warm-up to
+    ``--learning_rate``, then the decay to 0;
+  * ``--clip-grad-norm N``: global-norm gradient clipping;
+  * ``--trust-coefficient`` (default 0.001): LARS's trust coefficient.
+``--optimizer sgd`` with a schedule or clipping runs ``LARS(trust_coefficient=None)``: the same
+update as SGD with a device-side learning rate.  With a schedule active the step log line and
+``metrics.json`` carry ``lr``.
 """
 from __future__ import annotations
 
@@ -53,6 +65,28 @@ from mipipe.train import checkpoint as ckpt
 from mipipe.obs.meter import ThroughputMeter
 
 best_acc1 = 0.0
+
+
+def _make_optimizer(args, params, shadow_dtype):
+    """The run's optimizer.  The default flags give the reference's SGD (task.py:212-214) exactly
+    as before; a schedule, a warm-up or clipping with ``--optimizer sgd`` gives the same update
+    rule as ``LARS(trust_coefficient=None)``, whose learning rate lives on the device."""
+    plain = (args.lr_schedule == "constant" and args.lr_warmup_steps == 0
+             and args.clip_grad_norm is None)
+    if args.optimizer == "sgd" and plain:
+        return SGD(params, args.learning_rate, momentum=args.momentum,
+                   weight_decay=args.weight_decay, shadow_dtype=shadow_dtype)
+    from mipipe.optim import LAMB, LARS, LRSchedule
+    sched = LRSchedule(args.lr_schedule, args.learning_rate, args.lr_warmup_steps,
+                       args.lr_total_steps or 0)
+    if args.optimizer == "lamb":
+        return LAMB(params, sched, weight_decay=args.weight_decay,
+                    max_grad_norm=args.clip_grad_norm, shadow_dtype=shadow_dtype)
+    lars = args.optimizer == "lars"
+    # sgd: decay on every parameter, as the reference's SGD has it
+    return LARS(params, sched, momentum=args.momentum, weight_decay=args.weight_decay,
+                trust_coefficient=args.trust_coefficient if lars else None,
+                max_grad_norm=args.clip_grad_norm, exclude_1d=lars, shadow_dtype=shadow_dtype)
 
 
 def set_random_seeds(random_seed: int = 0) -> None:
@@ -154,6 +188,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--momentum", default=0.9, type=float, metavar="M", help="momentum")
     p.add_argument("--wd", "--weight-decay", default=1e-4, type=float, metavar="W",
                    dest="weight_decay", help="weight decay (default: 1e-4)")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars", "lamb"],
+                   help="sgd (default), lars (vision, large batch) or lamb (BERT, large batch)")
+    p.add_argument("--lr-schedule", default="constant",
+                   choices=["constant", "linear", "poly", "cosine"],
+                   help="learning-rate decay after the warm-up, evaluated on the device")
+    p.add_argument("--lr-warmup-steps", type=int, default=0, help="linear warm-up steps")
+    p.add_argument("--lr-total-steps", type=int, default=None,
+                   help="steps until the schedule ends (default: num_epochs x steps per epoch)")
+    p.add_argument("--clip-grad-norm", type=float, default=None,
+                   help="clip the global gradient norm to this value")
+    p.add_argument("--trust-coefficient", type=float, default=0.001,
+                   help="LARS trust coefficient")
     p.add_argument("--pretrained", dest="pretrained", action="store_true",
                    help="use pre-trained model: torchvision-format weights from "
                         "--pretrained-weights or the torchvision cache (no network download)")
@@ -373,9 +419,10 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
     elif use_gpu and args.gpu is None and _ngpus() > 1:
         model = DataParallel(model)  # task.py:201-208 path (d), on this replica's GPUs
     criterion = CrossEntropyLoss().to(device)
-    optimizer = SGD(model.parameters(), args.learning_rate, momentum=args.momentum,
-                    weight_decay=args.weight_decay,
-                    shadow_dtype=compute_dtype if compute_dtype != torch.float32 else None)
+    optimizer = _make_optimizer(args, model.parameters(),
+                                compute_dtype if compute_dtype != torch.float32 else None)
+    scheduled = not isinstance(optimizer, SGD) and (
+        args.lr_schedule != "constant" or args.lr_warmup_steps > 0)
 
     start_epoch = 0
     if args.resume:
@@ -439,6 +486,10 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         train_loader = DeviceBatchLoader(train_set, args.batch_size, train_sampler, device)
         test_loader = DeviceBatchLoader(test_set, 128, test_sampler, device)
 
+    if not isinstance(optimizer, SGD) and args.lr_total_steps is None and start_epoch == 0:
+        # the schedule ends with the run (its parameters are read from the group at every step)
+        per_epoch = min(len(train_loader), args.steps) if args.steps else len(train_loader)
+        optimizer.param_groups[0]["total_steps"] = args.num_epochs * per_epoch
     meter = ThroughputMeter(device, warmup_steps=args.warmup_steps)
     jlog = JsonlLogger(args.rank, args.log_dir or None)
     if args.trace:
@@ -517,10 +568,13 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                 if isinstance(model, DistributedDataParallel):
                     model.check_comm_errors()  # a one-shot wait that gave up -> error, no sync
                 last_loss = float(loss.detach().float().item())
+                # the LR the last step used, as its kernels computed it on the device
+                lr_kw = {"lr": float(optimizer.last_lr().item())} if scheduled else {}
                 jlog.log("step", epoch=epoch, step=global_step, loss=last_loss,
-                         samples_per_sec=meter.samples_per_sec())
+                         samples_per_sec=meter.samples_per_sec(), **lr_kw)
                 if args.rank == 0:
-                    print(f"epoch {epoch} step {global_step} loss {last_loss:.4f} "
+                    lr_txt = f" lr {lr_kw['lr']:.6g}" if scheduled else ""
+                    print(f"epoch {epoch} step {global_step} loss {last_loss:.4f}{lr_txt} "
                           f"{meter.samples_per_sec() * world:.1f} samples/s (job)", flush=True)
         if args.rank == 0:
             ckpt.save_checkpoint(model, optimizer, args, epoch + 1, best_acc1)
@@ -540,6 +594,8 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                "backend": (torch.distributed.get_backend() if args.distributed else "none"),
                "hip_graph": bool(args.hip_graph), "deterministic": bool(args.deterministic),
                "fused_eval": fused}
+    if scheduled:
+        metrics["lr"] = float(optimizer.last_lr().item())
     if args.rank == 0:
         ckpt.export_model(model, args, args.num_epochs, accuracy)
         ckpt.save_checkpoint(model, optimizer, args, args.num_epochs, best_acc1)
