@@ -56,6 +56,16 @@ float* fptr(const optional<Tensor>& t, int64_t n) {
   check_vec(*t, n, "gradient accumulator");
   return t->data_ptr<float>();
 }
+// an on/off environment switch (unset: dflt); callers keep the result in a static: read once
+bool env_flag(const char* name, bool dflt) {
+  const char* v = getenv(name);
+  return v == nullptr ? dflt : atoi(v) != 0;
+}
+// fp32 workspace of a split-K conv plan (n elements; n == 0: no split, undefined / null)
+Tensor split_ws(long n, const Tensor& like) {
+  return n > 0 ? torch::empty({n}, like.options().dtype(at::kFloat)) : Tensor();
+}
+float* wsp(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 
 // bf16 operands go through buffer descriptors with 32-bit byte offsets (gemm_core.hpp kOOB,
 // gk_rsrc clamps the range): a larger bf16 tensor would read zeros, so every conv entry point
@@ -67,21 +77,36 @@ void check_conv_buf_bytes(const mipipe::ConvShape& s, bool f32, const char* what
               "bf16 ", what, " tensors beyond 2 GiB are not supported");
 }
 
+// The one place a ConvShape is filled: sizes, strides / paddings in the struct's conventions
+// (stride_w 0 = same as stride, pad_w -1 = same as pad) and the output extent.  The callers
+// check what their kernels need.
+mipipe::ConvShape make_conv_shape(int64_t N, int64_t H, int64_t W, int64_t Ci, int64_t Co, int KH,
+                                  int KW, int stride, int pad, int stride_w, int pad_w, bool f32) {
+  mipipe::ConvShape s;
+  s.N = (int)N; s.H = (int)H; s.W = (int)W; s.Ci = (int)Ci;
+  s.Co = (int)Co; s.KH = KH; s.KW = KW; s.stride = stride; s.pad = pad;
+  s.stride_w = stride_w > 0 ? stride_w : 0;
+  s.pad_w = pad_w >= 0 ? pad_w : -1;
+  s.f32 = f32;
+  s.Ho = (s.H + 2 * pad - KH) / stride + 1;
+  s.Wo = (s.W + 2 * (pad_w >= 0 ? pad_w : pad) - KW) / (stride_w > 0 ? stride_w : stride) + 1;
+  return s;
+}
+// implicit-GEMM rows and 64-deep k-steps of the forward, and of the data-grad (run as a forward
+// convolution of dy), as the tuner's candidate lists need them
+long conv_rows(const mipipe::ConvShape& s) { return (long)s.N * s.Ho * s.Wo; }
+int conv_ksteps(const mipipe::ConvShape& s) { return (int)(((long)s.KH * s.KW * s.Ci + 63) / 64); }
+long conv_dgrad_rows(const mipipe::ConvShape& s) { return (long)s.N * s.H * s.W; }
+int conv_dgrad_ksteps(const mipipe::ConvShape& s) { return (int)(((long)s.KH * s.KW * s.Co + 63) / 64); }
+
 mipipe::ConvShape conv_shape(const Tensor& x, const Tensor& w, int stride, int pad,
                              int stride_w = 0, int pad_w = -1) {
   TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "conv expects NHWC x and [Co,KH,KW,Ci] w");
-  mipipe::ConvShape s;
-  s.N = (int)x.size(0); s.H = (int)x.size(1); s.W = (int)x.size(2); s.Ci = (int)x.size(3);
-  s.Co = (int)w.size(0); s.KH = (int)w.size(1); s.KW = (int)w.size(2);
-  TORCH_CHECK(w.size(3) == s.Ci, "weight Ci ", w.size(3), " != input channels ", s.Ci);
+  TORCH_CHECK(w.size(3) == x.size(3), "weight Ci ", w.size(3), " != input channels ", (int)x.size(3));
   TORCH_CHECK(stride >= 1 && pad >= 0, "bad stride/pad");
-  s.stride = stride; s.pad = pad;
-  s.stride_w = stride_w > 0 ? stride_w : 0;
-  s.pad_w = pad_w >= 0 ? pad_w : -1;
-  const int sw = stride_w > 0 ? stride_w : stride;
-  const int pw = pad_w >= 0 ? pad_w : pad;
-  s.Ho = (s.H + 2 * pad - s.KH) / stride + 1;
-  s.Wo = (s.W + 2 * pw - s.KW) / sw + 1;
+  const auto s = make_conv_shape(x.size(0), x.size(1), x.size(2), x.size(3), w.size(0),
+                                 (int)w.size(1), (int)w.size(2), stride, pad, stride_w, pad_w,
+                                 is_f32(x));
   TORCH_CHECK(s.Ho > 0 && s.Wo > 0, "empty conv output");
   TORCH_CHECK(s.Ci % 8 == 0, "conv kernels need Ci % 8 == 0 (pad channels), got ", s.Ci);
   TORCH_CHECK(x.numel() < (1ll << 31), "conv input too large for 32-bit gather offsets");
@@ -89,7 +114,7 @@ mipipe::ConvShape conv_shape(const Tensor& x, const Tensor& w, int stride, int p
   TORCH_CHECK((int64_t)s.N * s.H * s.W * s.Ci < (1ll << 31) &&
                   (int64_t)s.N * s.Ho * s.Wo * s.Co < (1ll << 31),
               "conv tensors beyond 2^31 elements are not supported");
-  check_conv_buf_bytes(s, x.scalar_type() == at::kFloat, "conv");
+  check_conv_buf_bytes(s, s.f32, "conv");
   return s;
 }
 
@@ -154,10 +179,7 @@ int select_from(const std::string& k, const std::vector<int>& cands, F&& run) {
   std::string log;
   // MIPIPE_TUNE_COLD=1: time every launch after a 512 MB sweep of the caches (operands as cold as
   // in a training step, where most were last touched a pass earlier) instead of back-to-back
-  static const bool cold = [] {
-    const char* v = getenv("MIPIPE_TUNE_COLD");
-    return v != nullptr && atoi(v) != 0;
-  }();
+  static const bool cold = env_flag("MIPIPE_TUNE_COLD", false);
   static void* sweep = nullptr;
   constexpr size_t kSweep = 512u << 20;
   if (cold && sweep == nullptr && hipMalloc(&sweep, kSweep) != hipSuccess) sweep = nullptr;
@@ -202,14 +224,11 @@ int select(const std::string& k, bool f32, bool wgrad, F&& run) {
   return select_from(k, candidates(f32, wgrad), run);
 }
 
-// Conv forward / forward-style data-grad plans (launchers.hpp kConvSplitPlan): every tile, plus
+// Conv forward / forward-style data-grad plans (plan.hpp decode_conv_plan): every tile, plus
 // split-K plans of the tiles whose output tiles alone leave the chip under-filled (fewer than
 // two blocks per CU; at least two k-steps per split).
 std::vector<int> conv_plan_candidates(bool f32, long M, long N, int nk) {
-  static const bool on = [] {  // MIPIPE_CONV_SPLIT=0: no split-K plans (A/B)
-    const char* v = getenv("MIPIPE_CONV_SPLIT");
-    return v == nullptr || atoi(v) != 0;
-  }();
+  static const bool on = env_flag("MIPIPE_CONV_SPLIT", true);  // =0: no split-K plans (A/B)
   std::vector<int> c;
   for (int t : candidates(f32, false)) {
     c.push_back(t);
@@ -220,14 +239,12 @@ std::vector<int> conv_plan_candidates(bool f32, long M, long N, int nk) {
     const long tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
     if (tiles >= 512) continue;
     for (int sp : {2, 3, 4, 6, 8})
-      if (nk >= 2 * sp && tiles * sp <= 4096) c.push_back(t + mipipe::kConvSplitPlan * sp);
+      if (nk >= 2 * sp && tiles * sp <= 4096) c.push_back(mipipe::encode_conv_plan(t, sp));
   }
   return c;
 }
 
-// GEMM plans: tile id + 16 * split-K count (0 = heuristic split; accumulating GEMMs only)
-constexpr int kPlanSplit = 16;
-constexpr int kPlanWs = 1024;  // gemm plans: split-K through per-split workspace slices
+// GEMM plans (plan.hpp decode_gemm_plan): split counts for the accumulating GEMMs only
 std::vector<int> gemm_candidates(bool f32, bool accumulate) {
   std::vector<int> c;
   for (int t : candidates(f32, accumulate)) {
@@ -235,7 +252,7 @@ std::vector<int> gemm_candidates(bool f32, bool accumulate) {
       c.push_back(t);
       continue;
     }
-    for (int sp : {1, 2, 4}) c.push_back(t + kPlanSplit * sp);
+    for (int sp : {1, 2, 4}) c.push_back(mipipe::encode_gemm_plan(t, sp, false));
   }
   return c;
 }
@@ -260,8 +277,7 @@ std::tuple<Tensor, optional<Tensor>, optional<Tensor>> conv_fwd(Tensor x, Tensor
   check_act(x, "x");
   check_same(w, x, "w");
   c10::DeviceGuard g(x.device());
-  auto s = conv_shape(x, w, stride, pad, stride_w, pad_w);
-  s.f32 = is_f32(x);
+  const auto s = conv_shape(x, w, stride, pad, stride_w, pad_w);
   // folded input BatchNorm: x holds y, the conv consumes relu(y*in_scale + in_bias)
   const float* isc = nullptr;
   const float* ibi = nullptr;
@@ -307,15 +323,8 @@ std::tuple<Tensor, optional<Tensor>, optional<Tensor>> conv_fwd(Tensor x, Tensor
     sh = shift->data_ptr<float>();
   }
   const float* bp = bias.has_value() ? bias->data_ptr<float>() : nullptr;
-  auto split_ws = [&](int plan) -> Tensor {  // fp32 workspace of a split-K plan (else empty)
-    const long n = mipipe::conv_fwd_split_ws_elems(s, plan);
-    return n > 0 ? torch::empty({n}, x.options().dtype(at::kFloat)) : Tensor();
-  };
-  auto wsp = [](const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
   if (cfg < 0) {
-    const long M = (long)s.N * s.Ho * s.Wo;
-    const int nk = (int)(((long)s.KH * s.KW * s.Ci + 63) / 64);
-    std::vector<int> cands = tune::conv_plan_candidates(s.f32, M, s.Co, nk);
+    std::vector<int> cands = tune::conv_plan_candidates(s.f32, conv_rows(s), s.Co, conv_ksteps(s));
     if (isc != nullptr) {  // folded-BN variant: 4-wave tiles, no split
       cands.clear();
       for (int t : tune::candidates(false, false))
@@ -328,15 +337,15 @@ std::tuple<Tensor, optional<Tensor>, optional<Tensor>> conv_fwd(Tensor x, Tensor
         a = torch::zeros_like(*ps);
         b = torch::zeros_like(*pss);
       }
-      Tensor ws = split_ws(c);
+      Tensor ws = split_ws(mipipe::conv_fwd_split_ws_elems(s, c), x);
       mipipe::conv_fwd(x.data_ptr(), w.data_ptr(), ys.data_ptr(),
                        a.has_value() ? a->data_ptr<float>() : nullptr,
                        b.has_value() ? b->data_ptr<float>() : nullptr, sh, s, stream(), bp, relu, c,
                        0, nullptr, wsp(ws), isc, ibi);
     });
   }
-  if (isc != nullptr && mipipe::conv_plan_tile(cfg) >= 11) cfg = -1;  // (a table from elsewhere)
-  Tensor ws = split_ws(cfg);
+  if (isc != nullptr && mipipe::decode_conv_plan(cfg).tile >= 11) cfg = -1;  // (a table from elsewhere)
+  Tensor ws = split_ws(mipipe::conv_fwd_split_ws_elems(s, cfg), x);
   if (mipipe::g_deterministic && psp != nullptr) {
     // per-M-tile partial rows (no atomics), then a fixed-order sum into slab row 0; the other
     // replica rows of the slabs stay zero
@@ -365,8 +374,7 @@ Tensor conv_fwd_infer(Tensor x, Tensor w, int stride, int pad, optional<Tensor> 
   check_act(x, "x");
   check_same(w, x, "w");
   c10::DeviceGuard g(x.device());
-  auto s = conv_shape(x, w, stride, pad, stride_w, pad_w);
-  s.f32 = is_f32(x);
+  const auto s = conv_shape(x, w, stride, pad, stride_w, pad_w);
   auto vec = [&](const optional<Tensor>& t, const char* name) -> const float* {
     if (!t.has_value()) return nullptr;
     check_vec(*t, s.Co, name);
@@ -383,23 +391,17 @@ Tensor conv_fwd_infer(Tensor x, Tensor w, int stride, int pad, optional<Tensor> 
                 ", got ", residual->sizes());
     rp = residual->data_ptr();
   }
-  auto split_ws = [&](int plan) -> Tensor {  // fp32 workspace of a split-K plan (else empty)
-    const long n = mipipe::conv_fwd_split_ws_elems(s, plan);
-    return n > 0 ? torch::empty({n}, x.options().dtype(at::kFloat)) : Tensor();
-  };
-  auto wsp = [](const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
   if (cfg < 0) {
-    const long M = (long)s.N * s.Ho * s.Wo;
-    const int nk = (int)(((long)s.KH * s.KW * s.Ci + 63) / 64);
     cfg = tune::select_from(tune::key(rp != nullptr ? "fwdinfr" : "fwdinf", s),
-                            tune::conv_plan_candidates(s.f32, M, s.Co, nk), [&](int c) {
+                            tune::conv_plan_candidates(s.f32, conv_rows(s), s.Co, conv_ksteps(s)),
+                            [&](int c) {
       auto ys = torch::empty_like(y);
-      Tensor ws = split_ws(c);
+      Tensor ws = split_ws(mipipe::conv_fwd_split_ws_elems(s, c), x);
       mipipe::conv_fwd_infer(x.data_ptr(), w.data_ptr(), ys.data_ptr(), s, stream(), scp, shp, rp,
                              relu, c, wsp(ws));
     });
   }
-  Tensor ws = split_ws(cfg);
+  Tensor ws = split_ws(mipipe::conv_fwd_split_ws_elems(s, cfg), x);
   mipipe::conv_fwd_infer(x.data_ptr(), w.data_ptr(), y.data_ptr(), s, stream(), scp, shp, rp, relu,
                          cfg, wsp(ws));
   return y;
@@ -415,15 +417,11 @@ Tensor conv_dgrad(Tensor dy, Tensor w, std::vector<int64_t> x_shape, int stride,
   check_same(w, dy, "w");
   c10::DeviceGuard g(dy.device());
   TORCH_CHECK(x_shape.size() == 4, "x_shape must be [N,H,W,Ci]");
-  mipipe::ConvShape s;
-  s.f32 = is_f32(dy);
-  s.N = (int)x_shape[0]; s.H = (int)x_shape[1]; s.W = (int)x_shape[2]; s.Ci = (int)x_shape[3];
-  s.Co = (int)w.size(0); s.KH = (int)w.size(1); s.KW = (int)w.size(2);
+  // (the data-grad has no horizontal stride of its own: stride_w stays 0)
+  const auto s = make_conv_shape(x_shape[0], x_shape[1], x_shape[2], x_shape[3], w.size(0),
+                                 (int)w.size(1), (int)w.size(2), stride, pad, 0, pad_w, is_f32(dy));
   TORCH_CHECK(w.size(3) == s.Ci, "weight/input channel mismatch");
-  s.stride = stride; s.pad = pad; s.pad_w = pad_w >= 0 ? pad_w : -1;
   const int pw = pad_w >= 0 ? pad_w : pad;
-  s.Ho = (s.H + 2 * pad - s.KH) / stride + 1;
-  s.Wo = (s.W + 2 * pw - s.KW) / stride + 1;
   TORCH_CHECK(dy.size(0) == s.N && dy.size(1) == s.Ho && dy.size(2) == s.Wo && dy.size(3) == s.Co,
               "dy shape does not match the convolution");
   TORCH_CHECK(s.Ci % 8 == 0 && s.Co % 8 == 0, "conv dgrad needs Ci, Co % 8 == 0");
@@ -506,16 +504,13 @@ Tensor conv_dgrad(Tensor dy, Tensor w, std::vector<int64_t> x_shape, int stride,
     any = true;
   }
   // split-K plans apply to the forward-style classes only (they need the flipped weight)
-  auto split_ws = [&](int plan) -> Tensor {
-    const long n = wfp != nullptr ? mipipe::conv_dgrad_split_ws_elems(s, plan) : 0;
-    return n > 0 ? torch::empty({n}, dy.options().dtype(at::kFloat)) : Tensor();
+  auto dgrad_ws = [&](int plan) {
+    return split_ws(wfp != nullptr ? mipipe::conv_dgrad_split_ws_elems(s, plan) : 0, dy);
   };
-  auto wsp = [](const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
   if (cfg < 0) {
     std::vector<int> cands = tune::candidates(s.f32, false);
     if (wfp != nullptr && s.stride == 1)
-      cands = tune::conv_plan_candidates(s.f32, (long)s.N * s.H * s.W, s.Ci,
-                                         (int)(((long)s.KH * s.KW * s.Co + 63) / 64));
+      cands = tune::conv_plan_candidates(s.f32, conv_dgrad_rows(s), s.Ci, conv_dgrad_ksteps(s));
     cfg = tune::select_from(tune::key("dgrad", s), cands, [&](int c) {
       auto dxs = torch::empty_like(dx);
       mipipe::DgradFusion f2 = fz;
@@ -524,12 +519,12 @@ Tensor conv_dgrad(Tensor dy, Tensor w, std::vector<int64_t> x_shape, int stride,
         reps = torch::zeros_like(*bn_rep);
         f2.bn_rep = reps.data_ptr<float>();
       }
-      Tensor ws = split_ws(c);
+      Tensor ws = dgrad_ws(c);
       mipipe::conv_dgrad(dy.data_ptr(), w.data_ptr(), dxs.data_ptr(), s, stream(),
                          any ? &f2 : nullptr, c, wfp, preflipped, wsp(ws));
     });
   }
-  Tensor ws = split_ws(cfg);
+  Tensor ws = dgrad_ws(cfg);
   if (mipipe::g_deterministic && fz.bn_rep != nullptr) {
     const int P = mipipe::conv_dgrad_tiles_m(s, cfg);
     const bool two = fz.bn_y2 != nullptr;
@@ -573,14 +568,8 @@ Tensor conv_wgrad(Tensor dy, Tensor x, int kh, int kw, int stride, int pad, opti
   check_act(dy, "dy");
   check_same(x, dy, "x");
   c10::DeviceGuard g(dy.device());
-  mipipe::ConvShape s;
-  s.f32 = is_f32(dy);
-  s.N = (int)x.size(0); s.H = (int)x.size(1); s.W = (int)x.size(2); s.Ci = (int)x.size(3);
-  s.Co = (int)dy.size(3); s.KH = kh; s.KW = kw; s.stride = stride; s.pad = pad;
-  s.stride_w = stride_w > 0 ? stride_w : 0;
-  s.pad_w = pad_w >= 0 ? pad_w : -1;
-  s.Ho = (s.H + 2 * pad - kh) / stride + 1;
-  s.Wo = (s.W + 2 * (pad_w >= 0 ? pad_w : pad) - kw) / (stride_w > 0 ? stride_w : stride) + 1;
+  const auto s = make_conv_shape(x.size(0), x.size(1), x.size(2), x.size(3), dy.size(3), kh, kw,
+                                 stride, pad, stride_w, pad_w, is_f32(dy));
   TORCH_CHECK(x.numel() < (1ll << 31), "conv wgrad input too large for 32-bit gather offsets");
   TORCH_CHECK(dy.size(0) == s.N && dy.size(1) == s.Ho && dy.size(2) == s.Wo, "dy/x mismatch");
   TORCH_CHECK(s.Ci % 8 == 0 && s.Co % 8 == 0, "conv wgrad needs Ci, Co % 8 == 0");
@@ -636,80 +625,49 @@ Tensor conv_wgrad(Tensor dy, Tensor x, int kh, int kw, int stride, int pad, opti
                           ws.data_ptr<float>(), S, colp);
     return dw;
   }
-  // plan = tile id + 16 * split count (0: heuristic split) [| kPlanWs: the split partial tiles
-  // go to workspace slices summed in order (the deterministic mode's path) instead of fp32
-  // atomics — cheaper where splits x Co x K x 4 B of atomics would run at ~1.3 TB/s]
-  int plan = cfg;
-  auto run_ws = [&](float* out, int tile, int sp) {
-    const int splits = mipipe::conv_wgrad_splits(s, tile, sp);
+  // a gemm plan (plan.hpp).  Plan::ws, and every split in deterministic mode: the split partial
+  // tiles go to workspace slices summed in order instead of fp32 atomics — cheaper where
+  // splits x Co x K x 4 B of atomics would run at ~1.3 TB/s
+  auto launch = [&](float* out, const mipipe::Plan& p, const mipipe::BnCollect* c) {
+    const int splits = mipipe::conv_wgrad_splits(s, p.tile, p.splits);
     if (splits == 1) {  // one writer per element: the plain read-modify-write is deterministic
-      mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), out, s, stream(), tile, nullptr, 1, colp, isc,
+      mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), out, s, stream(), p.tile, nullptr, 1, c, isc,
                          ibi);
       return;
     }
     auto ws = torch::empty({splits, (int64_t)s.Co * kh * kw * s.Ci}, dy.options().dtype(at::kFloat));
-    mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), out, s, stream(), tile, ws.data_ptr<float>(),
-                       sp, colp, isc, ibi);
+    mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), out, s, stream(), p.tile, ws.data_ptr<float>(),
+                       p.splits, c, isc, ibi);
   };
-  if (plan < 0) {
+  auto launch_atomic = [&](float* out, const mipipe::Plan& p, const mipipe::BnCollect* c) {
+    mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), out, s, stream(), p.tile, nullptr, p.splits, c,
+                       isc, ibi);
+  };
+  if (cfg < 0) {
+    // 3 / 6 / 12 / 24 splits as well: tiles x splits lands nearer a whole number of waves
+    // (MIPIPE_WGRAD_WIDE_SPLITS=0: powers of two only, A/B)
+    static const bool wide = env_flag("MIPIPE_WGRAD_WIDE_SPLITS", true);
+    static const bool ws_cands = env_flag("MIPIPE_WGRAD_WS", true);  // =0: atomic split-K only (A/B)
     std::vector<int> cands;
     for (int t : tune::candidates(s.f32, true)) {
       if (isc != nullptr && t >= 11) continue;  // folded-BN variant: 4-wave tiles
-      // 3 / 6 / 12 / 24 as well: tiles x splits lands nearer a whole number of waves
-      // (MIPIPE_WGRAD_WIDE_SPLITS=0: powers of two only, A/B)
-      static const bool wide = [] {
-        const char* v = getenv("MIPIPE_WGRAD_WIDE_SPLITS");
-        return v == nullptr || atoi(v) != 0;
-      }();
       for (int sp : {0, 1, 2, 3, 4, 6, 8, 12, 16})
-        if (wide || (sp & (sp - 1)) == 0) cands.push_back(t + tune::kPlanSplit * sp);
-      static const bool ws_cands = [] {  // MIPIPE_WGRAD_WS=0: atomic split-K only (A/B)
-        const char* v = getenv("MIPIPE_WGRAD_WS");
-        return v == nullptr || atoi(v) != 0;
-      }();
+        if (wide || (sp & (sp - 1)) == 0) cands.push_back(mipipe::encode_gemm_plan(t, sp, false));
       if (!mipipe::g_deterministic && ws_cands)
         for (int sp : {4, 6, 8, 12, 16, 24, 32})
-          if (wide || (sp & (sp - 1)) == 0) cands.push_back((t + tune::kPlanSplit * sp) | tune::kPlanWs);
+          if (wide || (sp & (sp - 1)) == 0) cands.push_back(mipipe::encode_gemm_plan(t, sp, true));
     }
-    plan = tune::select_from(tune::key(isc != nullptr ? "wgradbn" : "wgrad", s), cands, [&](int p) {
+    cfg = tune::select_from(tune::key(isc != nullptr ? "wgradbn" : "wgrad", s), cands, [&](int c) {
       auto dws = torch::zeros_like(dw);
-      const bool wsp = (p & tune::kPlanWs) != 0;
-      p &= ~tune::kPlanWs;
-      const int sp = p / tune::kPlanSplit;
-      if (wsp) {  // collect off while timing (col rides in the real launch only)
-        const int splits = mipipe::conv_wgrad_splits(s, p % tune::kPlanSplit, sp);
-        auto ws = torch::empty({splits, (int64_t)s.Co * kh * kw * s.Ci},
-                               dy.options().dtype(at::kFloat));
-        mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), dws.data_ptr<float>(), s, stream(),
-                           p % tune::kPlanSplit, ws.data_ptr<float>(), sp, nullptr, isc, ibi);
-        return;
-      }
-      mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), dws.data_ptr<float>(), s, stream(),
-                         p % tune::kPlanSplit, nullptr, sp > 0 ? sp : -1, nullptr, isc, ibi);
+      const mipipe::Plan p = mipipe::decode_gemm_plan(c, false);
+      // collect off while timing (col rides in the real launch only)
+      if (p.ws) launch(dws.data_ptr<float>(), p, nullptr);
+      else launch_atomic(dws.data_ptr<float>(), p, nullptr);
     });
   }
-  const bool ws_plan = plan >= 0 && (plan & tune::kPlanWs) != 0;
-  if (ws_plan) plan &= ~tune::kPlanWs;
-  const int tile = plan < 0 ? -1 : plan % tune::kPlanSplit;
-  const int sp = plan < 0 ? -1 : (plan / tune::kPlanSplit > 0 ? plan / tune::kPlanSplit : -1);
-  if (ws_plan && !mipipe::g_deterministic) {
-    run_ws(dw.data_ptr<float>(), tile, sp);
-    return dw;
-  }
-  if (mipipe::g_deterministic) {
-    const int splits = mipipe::conv_wgrad_splits(s, tile, sp);
-    if (splits == 1) {  // one writer per element: the plain read-modify-write is deterministic
-      mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr<float>(), s, stream(), tile,
-                         nullptr, 1, colp, isc, ibi);
-      return dw;
-    }
-    auto ws = torch::empty({splits, (int64_t)s.Co * kh * kw * s.Ci}, dy.options().dtype(at::kFloat));
-    mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr<float>(), s, stream(), tile,
-                       ws.data_ptr<float>(), sp, colp, isc, ibi);
-    return dw;
-  }
-  mipipe::conv_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr<float>(), s, stream(), tile,
-                     nullptr, sp, colp, isc, ibi);
+  const mipipe::Plan plan = mipipe::decode_gemm_plan(cfg, false);
+  if (plan.ws || mipipe::g_deterministic) launch(dw.data_ptr<float>(), plan, colp);
+  else launch_atomic(dw.data_ptr<float>(), plan, colp);
   return dw;
 }
 
@@ -1165,10 +1123,7 @@ constexpr long kTicketCap = 1 << 20;
 // agent-scope release / acquire fences around the ticket are an L2 write-back and an L2
 // INVALIDATE of the whole XCD (buffer_wbl2 / buffer_inv sc1): every block that finishes a split
 // throws away the operand tiles its neighbours on that XCD were reusing.
-bool g_ws_finish = [] {
-  const char* v = getenv("MIPIPE_WS_FINISH");
-  return v != nullptr && atoi(v) != 0;
-}();
+bool g_ws_finish = env_flag("MIPIPE_WS_FINISH", false);
 
 int* ws_tickets(const Tensor& like, long n) {
   if (!g_ws_finish || n <= 0 || n > kTicketCap) return nullptr;
@@ -1251,7 +1206,7 @@ Tensor gemm(Tensor a, Tensor b, bool trans_a, bool trans_b, optional<Tensor> bia
   //    splitk_sum_bf16 adds the slices, the bias / addend and rounds once to bf16.
   // Split counts 2..8 (not only powers of two): tiles x splits can then land near a whole
   // number of waves over the 256 CUs.
-  // Plans with kPlanWs set.  (Round 3 also timed a hipBLASLt "library plan" here; it is gone:
+  // Plans with Plan::ws set.  (Round 3 also timed a hipBLASLt "library plan" here; it is gone:
   // every GEMM of the training step runs on the MFMA kernels, tools/gemm_plans.py.)
   const bool ws_out0 = mode == 0 && act_i == 0 && N % 8 == 0;
   // another GEMM's cold operands, warmed by this one's blocks (mipipe/ops/prefetch.py)
@@ -1266,13 +1221,9 @@ Tensor gemm(Tensor a, Tensor b, bool trans_a, bool trans_b, optional<Tensor> bia
       pf.bytes[pf.count++] = (long)(t.numel() * t.element_size());
     }
   const mipipe::TouchRanges* pfp = pf.count > 0 ? &pf : nullptr;
-  auto launch = [&](void* C, int p) {
-    if (p >= 4096) p = -1;  // a round-3 table's library plan: the heuristic MFMA plan
-    const bool ws_plan = p >= 0 && (p & tune::kPlanWs) != 0;
-    if (ws_plan) p &= ~tune::kPlanWs;
-    const int cfg = p < 0 ? -1 : p % tune::kPlanSplit;
-    const int sp = p < 0 ? -1 : (p / tune::kPlanSplit > 0 ? p / tune::kPlanSplit : -1);
-    if (ws_plan && (mode == 2 || ws_out0) && sp > 1) {
+  auto launch = [&](void* C, const mipipe::Plan& p) {
+    const int cfg = p.tile, sp = p.splits;
+    if (p.ws && (mode == 2 || ws_out0) && sp > 1) {
       const int ns = mipipe::gemm_ws_splits((int)K, sp);
       Tensor ws = torch::empty({(int64_t)ns, M, N}, a.options().dtype(at::kFloat));
       mipipe::WsFinish fin;
@@ -1310,16 +1261,16 @@ Tensor gemm(Tensor a, Tensor b, bool trans_a, bool trans_b, optional<Tensor> bia
     const bool small_f32 = ws_out0 && f32 && K >= 256 && ((M + 127) / 128) * ((N + 63) / 64) < 256;
     if ((mode == 2 && K >= 1024) || (ws_out0 && K >= 2048) || small_f32) {
       for (int t : tune::candidates(f32, mode == 2))
-        for (int sp : {2, 3, 4, 6, 8}) cands.push_back((t + tune::kPlanSplit * sp) | tune::kPlanWs);
+        for (int sp : {2, 3, 4, 6, 8}) cands.push_back(mipipe::encode_gemm_plan(t, sp, true));
     }
     plan = tune::select_from(tune::gemm_key(M, N, K, !trans_a, trans_b, add_p != nullptr ? 3 : mode, f32),
                              cands, [&](int p) {
                                auto scratch = mode == 2 ? torch::zeros_like(out)
                                                         : torch::empty_like(out);
-                               launch(scratch.data_ptr(), p);
+                               launch(scratch.data_ptr(), mipipe::decode_gemm_plan(p, true));
                              });
   }
-  launch(out.data_ptr(), (int)plan);
+  launch(out.data_ptr(), mipipe::decode_gemm_plan((int)plan, true));
   return out;
 }
 
@@ -1340,21 +1291,18 @@ std::tuple<Tensor, Tensor> gemm_gelu(Tensor a, Tensor b, optional<Tensor> bias, 
     bias_p = bias->data_ptr<float>();
   }
   auto y = torch::empty({M, N}, a.options()), h = torch::empty({M, N}, a.options());
-  auto launch = [&](void* yo, void* ho, int p) {
-    if (p >= 0) p &= ~tune::kPlanWs;  // a workspace plan of the plain GEMM: its tile
-    if (p >= 4096) p = -1;
-    const int cfg = p < 0 ? -1 : p % tune::kPlanSplit;
+  auto launch = [&](void* yo, void* ho, const mipipe::Plan& p) {  // (a plain-GEMM plan: its tile)
     mipipe::gemm(a.data_ptr(), K, true, b.data_ptr(), K, true, yo, N, (int)M, (int)N, (int)K,
-                 bias_p, 2, 0, stream(), false, cfg, -1, nullptr, false, nullptr, ho);
+                 bias_p, 2, 0, stream(), false, p.tile, -1, nullptr, false, nullptr, ho);
   };
   if (plan < 0) {
     plan = tune::select_from(tune::gemm_key(M, N, K, true, true, 0, false),
                              tune::gemm_candidates(false, false), [&](int p) {
                                auto ys = torch::empty_like(y), hs = torch::empty_like(h);
-                               launch(ys.data_ptr(), hs.data_ptr(), p);
+                               launch(ys.data_ptr(), hs.data_ptr(), mipipe::decode_gemm_plan(p, true));
                              });
   }
-  launch(y.data_ptr(), h.data_ptr(), (int)plan);
+  launch(y.data_ptr(), h.data_ptr(), mipipe::decode_gemm_plan((int)plan, true));
   return {y, h};
 }
 
@@ -2310,11 +2258,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("dgrad_preflip_ok", [](std::vector<int64_t> x_shape, std::vector<int64_t> w_shape,
                                int stride, int pad) {
     // whether conv_fwd(wflip=...) prepares this conv's data-grad weight (dgrad_preflip_ok)
-    mipipe::ConvShape s;
-    s.N = (int)x_shape[0]; s.H = (int)x_shape[1]; s.W = (int)x_shape[2]; s.Ci = (int)x_shape[3];
-    s.Co = (int)w_shape[0]; s.KH = (int)w_shape[1]; s.KW = (int)w_shape[2];
-    s.stride = stride; s.pad = pad; s.stride_w = 0; s.pad_w = -1;
-    return mipipe::dgrad_preflip_ok(s);
+    return mipipe::dgrad_preflip_ok(make_conv_shape(x_shape[0], x_shape[1], x_shape[2], x_shape[3],
+                                                    w_shape[0], (int)w_shape[1], (int)w_shape[2],
+                                                    stride, pad, 0, -1, false));
   });
   m.def("bn_bwd_collect", &bn_bwd_collect, py::arg("rep"), py::arg("C"),
         py::arg("dgamma") = py::none(), py::arg("dbeta") = py::none());
@@ -2347,9 +2293,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("get_deterministic", []() { return mipipe::g_deterministic != 0; });
   m.def("tune_table", []() { return tune::g_table; });
   m.def("set_tune_entry", [](const std::string& k, int cfg) {
-    // plans: tile id + 16 * (split-K count | direct-epilogue flag)
-    TORCH_CHECK(cfg == -1 || (cfg >= 0 && cfg % 16 < mipipe::kConvTileConfigs),
-                "bad tile plan id");
+    TORCH_CHECK(mipipe::plan_id_ok(cfg, mipipe::kConvTileConfigs), "bad tile plan id");
     if (cfg < 0) tune::g_table.erase(k);
     else tune::g_table[k] = cfg;
   });

@@ -14,7 +14,8 @@ int default_dgrad_cfg(const ConvShape& s, long K_class) {
   return ns1 ? 1 : 0;
 }
 
-// The parity classes of a stride-S dgrad: (class descriptor, rows M) in launch order.
+// The parity classes of a stride-S dgrad: (class descriptor, rows M, tap rows nkh) in launch
+// order (DgradClass carries ntaps and nkw only).
 template <class F>
 static void for_each_class(const ConvShape& s, F&& f) {
   const int S = s.stride;
@@ -39,20 +40,20 @@ static void for_each_class(const ConvShape& s, F&& f) {
       c.fnkw = FastDiv((uint32_t)c.nkw);
       c.fHcWc = FastDiv((uint32_t)(c.Hc * c.Wc));
       c.fWc = FastDiv((uint32_t)c.Wc);
-      f(c, (uint32_t)s.N * c.Hc * c.Wc);
+      f(c, (uint32_t)s.N * c.Hc * c.Wc, nkh);
     }
   }
 }
 
 static int resolve_dgrad_cfg(const ConvShape& s, int cfg, long K_class) {
-  cfg = conv_plan_tile(cfg);
+  cfg = decode_conv_plan(cfg).tile;
   const bool ok = s.f32 ? tile_ok_for<float>(cfg) : tile_ok_for<__bf16>(cfg);
   return ok ? cfg : default_dgrad_cfg(s, K_class);
 }
 
 int conv_dgrad_tiles_m(const ConvShape& s, int cfg_in) {
   int total = 0;
-  for_each_class(s, [&](const DgradClass& c, uint32_t M) {
+  for_each_class(s, [&](const DgradClass& c, uint32_t M, int) {
     const int cfg = resolve_dgrad_cfg(s, cfg_in, (long)c.ntaps * s.Co);
     int bm = 128;
     auto f = [&](auto tile) { bm = decltype(tile)::BM; };
@@ -90,15 +91,15 @@ int dgrad_fwd_style_mode() {
 // workspace of a split plan: the largest forward-style class's splits x rows x Ci (classes run
 // one after another on the stream and reuse it)
 long conv_dgrad_split_ws_elems(const ConvShape& s, int cfg) {
-  if (conv_plan_splits(cfg) <= 1 || dgrad_fwd_style_mode() <= 0 ||
+  if (decode_conv_plan(cfg).splits <= 1 || dgrad_fwd_style_mode() <= 0 ||
       !conv_dgrad_fwd_style(s, dgrad_fwd_style_mode() >= 2))
     return 0;
   long need = 0;
-  for_each_class(s, [&](const DgradClass& c, uint32_t M) {
+  for_each_class(s, [&](const DgradClass& c, uint32_t M, int) {
     if (c.ntaps <= 0) return;
     const int nk = (int)cdiv((uint64_t)c.ntaps * s.Co, BK);
     int S, kps;
-    conv_split_geometry(nk, conv_plan_splits(cfg), &S, &kps);
+    conv_split_geometry(nk, decode_conv_plan(cfg).splits, &S, &kps);
     if (S > 1) need = std::max(need, (long)S * M * s.Ci);
   });
   return need;
@@ -114,9 +115,8 @@ void dgrad_flip_plan(const ConvShape& s, FlipPlan& p) {
   p.S = s.stride;
   long off = 0;
   const uint32_t tiles = cdiv(s.Ci, 64) * cdiv(s.Co, 64);
-  for_each_class(s, [&](const DgradClass& c, uint32_t) {
+  for_each_class(s, [&](const DgradClass& c, uint32_t, int nkh) {
     if (c.ntaps <= 0 || p.ncls >= 4) return;
-    const int nkh = c.kh0 < s.KH ? (s.KH - c.kh0 + c.S - 1) / c.S : 0;
     FlipClass& f = p.cls[p.ncls++];
     f.kh0 = c.kh0; f.kw0 = c.kw0; f.nkh = nkh; f.nkw = c.nkw;
     f.off = off;
@@ -177,7 +177,7 @@ static void conv_dgrad_t(const void* dy, const void* w, void* dx, const ConvShap
   const int S = s.stride;
   FastDiv fCo((uint32_t)s.Co);
   int row0 = 0;  // deterministic mode: first partial row of this class
-  for_each_class(s, [&](const DgradClass& c, uint32_t M) {
+  for_each_class(s, [&](const DgradClass& c, uint32_t M, int nkh) {
       EpiParams e{};
       e.C = dx; e.ldc = s.Ci; e.M = M; e.N = s.Ci;
       e.nt = ((g_nt_store >> 1) & 1) &&
@@ -202,7 +202,6 @@ static void conv_dgrad_t(const void* dy, const void* w, void* dx, const ConvShap
       }
       const int taps = s.KH * s.KW;
       const int cfg = resolve_dgrad_cfg(s, cfg_in, (long)c.ntaps * s.Co);
-      const int nkh = c.kh0 < s.KH ? (s.KH - c.kh0 + S - 1) / S : 0;
       if (wflip != nullptr && c.ntaps > 0 && e.bnr_y2 == nullptr) {
         // this class as a stride-1 forward convolution of dy (see conv_dgrad_fwd_style)
         T* wt = (T*)wflip + flip_off;
@@ -220,7 +219,7 @@ static void conv_dgrad_t(const void* dy, const void* w, void* dx, const ConvShap
         const bool dense2 = dense && S == 1;
         int SK = 1, kps = 0;
         conv_split_geometry((int)cdiv((uint64_t)c.ntaps * s.Co, BK),
-                            split_ws != nullptr ? conv_plan_splits(cfg_in) : 1, &SK, &kps);
+                            split_ws != nullptr ? decode_conv_plan(cfg_in).splits : 1, &SK, &kps);
         with_tile<T>(cfg, [&](auto tile) {
           typedef decltype(tile) C;
           const uint32_t tN = cdiv(s.Ci, C::BN), tiles = cdiv(M, C::BM) * tN;

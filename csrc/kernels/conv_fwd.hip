@@ -19,7 +19,7 @@ int default_fwd_cfg(const ConvShape& s) {
 }
 
 int resolve_fwd_cfg(const ConvShape& s, int cfg) {
-  cfg = conv_plan_tile(cfg);
+  cfg = decode_conv_plan(cfg).tile;
   const bool ok = s.f32 ? tile_ok_for<float>(cfg) : tile_ok_for<__bf16>(cfg);
   return ok ? cfg : default_fwd_cfg(s);
 }
@@ -29,14 +29,14 @@ void conv_tile_dims(int cfg, bool f32, int* bm, int* bn) {
     *bm = decltype(tile)::BM;
     *bn = decltype(tile)::BN;
   };
-  if (f32) with_tile<float>(conv_plan_tile(cfg), f);
-  else with_tile<__bf16>(conv_plan_tile(cfg), f);
+  if (f32) with_tile<float>(decode_conv_plan(cfg).tile, f);
+  else with_tile<__bf16>(decode_conv_plan(cfg).tile, f);
 }
 
 long conv_fwd_split_ws_elems(const ConvShape& s, int cfg) {
   const int nk = (int)cdiv((uint64_t)s.KH * s.KW * s.Ci, BK);
   int S, kps;
-  conv_split_geometry(nk, conv_plan_splits(cfg), &S, &kps);
+  conv_split_geometry(nk, decode_conv_plan(cfg).splits, &S, &kps);
   return S > 1 ? (long)S * s.N * s.Ho * s.Wo * s.Co : 0;
 }
 
@@ -75,7 +75,7 @@ static void conv_fwd_t(const void* x, const void* w, void* y, float* st_sum, flo
   const T* wp = (const T*)w;
   const int nk = (int)cdiv((uint64_t)s.KH * s.KW * s.Ci, BK);
   int S, kps;
-  conv_split_geometry(nk, split_ws != nullptr ? conv_plan_splits(cfg) : 1, &S, &kps);
+  conv_split_geometry(nk, split_ws != nullptr ? decode_conv_plan(cfg).splits : 1, &S, &kps);
   cfg = resolve_fwd_cfg(s, cfg);
   if (in_scale != nullptr) {  // folded input BN: dense bf16, 4-wave tiles, no split
     e.in_scale = in_scale;
@@ -128,7 +128,7 @@ static int conv_fwd_split_partials_t(const void* x, const void* w, const ConvSha
                                      hipStream_t st, int cfg, float* split_ws) {
   const int nk = (int)cdiv((uint64_t)s.KH * s.KW * s.Ci, BK);
   int S, kps;
-  conv_split_geometry(nk, conv_plan_splits(cfg), &S, &kps);
+  conv_split_geometry(nk, decode_conv_plan(cfg).splits, &S, &kps);
   if (S <= 1) return 1;
   ConvGeom g = make_geom(s);
   const uint32_t M = (uint32_t)s.N * s.Ho * s.Wo;

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plan.hpp"
+
 namespace mipipe {
 
 // ---- convolution (NHWC activations, weights [Co][KH][KW][Ci]) --------------------------------
@@ -95,14 +97,11 @@ inline bool conv_is_dense(const ConvShape& s) {  // 1x1, stride 1, no padding
 // in_scale / in_bias (bf16 dense 1x1, Ci <= 1024): x holds y of a BatchNorm + ReLU whose apply is
 // FOLDED into this conv — the conv consumes relu(y*in_scale + in_bias) (per input channel),
 // transformed after each operand fragment's LDS read; the normalised tensor never exists.
-// Conv forward / forward-style data-grad PLANS: tile id + kConvSplitPlan * splits.  A split plan
+// Conv forward / forward-style data-grad PLANS (plan.hpp decode_conv_plan).  A split plan
 // (splits >= 2) runs the k-steps in `splits` slices (grid.y) into an fp32 workspace and a finish
 // launch sums the slices in slice order (deterministic) and runs the regular epilogue — for the
 // small-spatial layers whose tiles alone cannot fill 256 CUs (ResNet-18 32x32 layer 3 / 4: 64-128
 // tiles of 36 k-steps each).
-constexpr int kConvSplitPlan = 16;
-inline int conv_plan_tile(int plan) { return plan < 0 ? plan : plan % kConvSplitPlan; }
-inline int conv_plan_splits(int plan) { return plan < kConvSplitPlan ? 1 : plan / kConvSplitPlan; }
 // (effective splits, k-steps per split) of nk k-steps under a plan's split request
 inline void conv_split_geometry(int nk, int req, int* splits, int* kps) {
   if (req <= 1 || nk < 2) {
