@@ -1390,6 +1390,93 @@ std::tuple<Tensor, Tensor> cross_entropy_fwd_bwd(Tensor logits, Tensor labels, d
   return {loss, grad};
 }
 
+// the device-side mix descriptor (mipipe/data/mix.py): fp32, >= 8 elements, on `ref`'s device
+void check_mix(const Tensor& mix, const Tensor& ref) {
+  check_f32(mix, "mix");
+  TORCH_CHECK(mix.numel() >= 8, "mix must hold at least 8 elements, got ", mix.numel());
+  TORCH_CHECK(mix.device() == ref.device(), "mix must be on the device of the other operands");
+}
+
+// Pair-target split cross-entropy (Mixup / CutMix): row r is labelled labels[r] with weight
+// mix[0] and labels[R-1-r] with weight 1 - mix[0]; same work layout as cross_entropy_fwd.
+std::tuple<Tensor, Tensor> cross_entropy_mixed_fwd(Tensor logits, Tensor labels, Tensor mix,
+                                                   double smoothing, int64_t valid_cols) {
+  check_act(logits, "logits");
+  check_cuda(labels, "labels");
+  check_mix(mix, logits);
+  c10::DeviceGuard g(logits.device());
+  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
+  TORCH_CHECK(logits.dim() == 2 && labels.numel() == logits.size(0) && logits.is_contiguous(),
+              "CE shape mismatch");
+  TORCH_CHECK(labels.device() == logits.device(), "labels must be on the logits' device");
+  const int R = logits.size(0), V = logits.size(1);
+  auto loss = torch::empty({}, logits.options().dtype(at::kFloat));
+  auto work = torch::empty({4 + 2 * (int64_t)R}, logits.options().dtype(at::kInt));
+  if (R == 0 || V == 0) return {loss.zero_(), work};
+  mipipe::cross_entropy_mixed_fwd(
+      logits.data_ptr(), labels.data_ptr<int64_t>(), mix.data_ptr<float>(),
+      loss.data_ptr<float>(), R, V, (float)smoothing, work.data_ptr<int>(), stream(),
+      is_f32(logits), (int)std::min<int64_t>(valid_cols > 0 ? valid_cols : V, V));
+  return {loss, work};
+}
+
+Tensor cross_entropy_mixed_bwd(Tensor logits, Tensor labels, Tensor mix, Tensor work, Tensor gout,
+                               double smoothing, int64_t valid_cols) {
+  check_act(logits, "logits");
+  check_mix(mix, logits);
+  c10::DeviceGuard g(logits.device());
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && labels.numel() == logits.size(0),
+              "CE shape mismatch");
+  const int R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == 4 + 2 * (int64_t)R,
+              "CE work buffer mismatch");
+  check_cuda(labels, "labels");
+  check_cuda(work, "work");
+  check_f32(gout, "gout");
+  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
+  TORCH_CHECK(gout.numel() == 1 && gout.device() == logits.device() &&
+              labels.device() == logits.device() && work.device() == logits.device(),
+              "gout must be one value; every operand on the logits' device");
+  auto grad = torch::empty_like(logits);
+  if (R == 0 || V == 0) return grad;
+  mipipe::cross_entropy_mixed_bwd(
+      logits.data_ptr(), labels.data_ptr<int64_t>(), mix.data_ptr<float>(), work.data_ptr<int>(),
+      gout.data_ptr<float>(), grad.data_ptr(), R, V, (float)smoothing, stream(), is_f32(logits),
+      (int)std::min<int64_t>(valid_cols > 0 ? valid_cols : V, V));
+  return grad;
+}
+
+// Mixup / CutMix of x [B, C, H, W] with its reverse, as the device descriptor says (mix.hip).
+// out: x itself (in place), another tensor of x's shape and type, or none (a new tensor).
+Tensor batch_mix(Tensor x, Tensor mix, optional<Tensor> out) {
+  check_act(x, "x");
+  check_mix(mix, x);
+  c10::DeviceGuard g(x.device());
+  TORCH_CHECK(x.dim() == 4, "x must be [B, C, H, W], got ", x.dim(), " dimensions");
+  const int64_t B = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(B < (1ll << 31) && C * H * W < (1ll << 31), "sample too large: C*H*W must be < 2^31");
+  Tensor o = out.has_value() ? *out : torch::empty_like(x);
+  if (out.has_value()) {
+    check_same(o, x, "out");
+    TORCH_CHECK(o.sizes() == x.sizes() && o.device() == x.device(),
+                "out must have x's shape and device");
+    const char* xb = static_cast<const char*>(x.data_ptr());
+    const char* ob = static_cast<const char*>(o.data_ptr());
+    const int64_t nb = (int64_t)x.numel() * x.element_size();
+    TORCH_CHECK(ob == xb || ob + nb <= xb || xb + nb <= ob, "out overlaps x without being x");
+  }
+  {
+    const char* mb = static_cast<const char*>(mix.data_ptr());
+    const char* ob = static_cast<const char*>(o.data_ptr());
+    const int64_t nb = (int64_t)o.numel() * o.element_size();
+    TORCH_CHECK(mb + mix.numel() * 4 <= ob || ob + nb <= mb, "mix overlaps out");
+  }
+  if (x.numel() == 0) return o;
+  mipipe::batch_mix(x.data_ptr(), o.data_ptr(), mix.data_ptr<float>(), (int)B, (int)C, (int)H,
+                    (int)W, is_f32(x), stream());
+  return o;
+}
+
 // number of rows whose argmax equals the label, accumulated into an int32 device counter
 Tensor top1_correct(Tensor logits, Tensor labels, optional<Tensor> out) {
   check_act(logits, "logits");
@@ -2360,6 +2447,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("ignore_index") = -100, py::arg("valid_cols") = -1);
   m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd, py::arg("logits"), py::arg("labels"),
         py::arg("smoothing"), py::arg("ignore_index"), py::arg("valid_cols") = -1);
+  m.def("cross_entropy_mixed_fwd", &cross_entropy_mixed_fwd, py::arg("logits"), py::arg("labels"),
+        py::arg("mix"), py::arg("smoothing") = 0.0, py::arg("valid_cols") = -1);
+  m.def("cross_entropy_mixed_bwd", &cross_entropy_mixed_bwd, py::arg("logits"), py::arg("labels"),
+        py::arg("mix"), py::arg("work"), py::arg("gout"), py::arg("smoothing") = 0.0,
+        py::arg("valid_cols") = -1);
+  m.def("batch_mix", &batch_mix, py::arg("x"), py::arg("mix"), py::arg("out") = py::none());
   m.def("sgd_step", &sgd_step);
   m.def("adamw_step", &adamw_step, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"),
         py::arg("shadow"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),

@@ -358,6 +358,19 @@ void cross_entropy_fwd(const void* logits, const int64_t* labels, float* loss, i
 void cross_entropy_bwd(const void* logits, const int64_t* labels, const int* work,
                        const float* gout, void* grad, int R, int V, float smoothing,
                        int64_t ignore_index, hipStream_t st, bool f32, int Vv);
+// Pair-target form of the split loss (Mixup / CutMix): row r's target is lambda on labels[r] and
+// 1 - lambda on labels[R-1-r], lambda = mix[0] read on the device by both kernels.  Every row
+// counts (no ignore_index); same work layout, same arithmetic as the hard-label kernels.
+void cross_entropy_mixed_fwd(const void* logits, const int64_t* labels, const float* mix,
+                             float* loss, int R, int V, float smoothing, int* work,
+                             hipStream_t st, bool f32, int Vv);
+void cross_entropy_mixed_bwd(const void* logits, const int64_t* labels, const float* mix,
+                             const int* work, const float* gout, void* grad, int R, int V,
+                             float smoothing, hipStream_t st, bool f32, int Vv);
+// Mixup / CutMix of x [B][C][H][W] with its reverse (mix.hip): sample i with sample B-1-i, as the
+// device descriptor mix (fp32[8]: lambda, mode, y0, y1, x0, x1) says.  out == x mixes in place.
+void batch_mix(const void* x, void* out, const float* mix, int B, int C, int H, int W, bool f32,
+               hipStream_t st);
 // *correct += #rows whose first maximal logit is at the label (torch.argmax tie rule)
 void top1_correct(const void* logits, const int64_t* labels, int R, int V, int* correct,
                   hipStream_t st, bool f32 = false);

@@ -165,13 +165,18 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float mo, float so
   m = mn;
 }
 
-template <class T>
+// MIX: the pair-target form (Mixup / CutMix).  Row r has the labels a = labels[r] and
+// b = labels[R-1-r] with weights lambda = mix[0] and 1 - lambda, read on the device; every row
+// counts (nvalid and ignore are unused).  lambda = 1 gives the hard-label result bit for bit:
+// 1 * x[a] + 0 * x[b] is x[a], and (1 - eps) * (1 * [c==a] + 0 * [c==b]) is 1 - eps or 0.
+template <class T, bool MIX = false>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logits,
                                                      const int64_t* __restrict__ labels, int V,
                                                      int Vv, float eps, int64_t ignore,
                                                      const int* __restrict__ nvalid,
                                                      float* __restrict__ rowloss,
-                                                     float* __restrict__ lse_out) {
+                                                     float* __restrict__ lse_out,
+                                                     const float* __restrict__ mix = nullptr) {
   __shared__ float sh[3][4];
   const long row = blockIdx.x;
   const T* x = logits + row * V;
@@ -224,29 +229,62 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
     }
     const float lse = M + __logf(S);
     const int64_t lab = labels[row];
+    bool valid = lab != ignore;
+    float xl = 0.f;
+    int n;
+    if constexpr (MIX) {
+      const int64_t lab2 = labels[(long)gridDim.x - 1 - row];
+      const float lam = mix[0], om = 1.f - lam;
+      // a label outside the classes reads nothing (its logit counts as 0)
+      const float xa = (uint64_t)lab < (uint64_t)Vv ? (float)x[lab] : 0.f;
+      const float xb = (uint64_t)lab2 < (uint64_t)Vv ? (float)x[lab2] : 0.f;
+      xl = lam * xa + om * xb;
+      valid = true;
+      n = (int)gridDim.x;
+    } else {
+      if (valid) xl = (float)x[lab];
+      n = nvalid[0];
+    }
     float l = 0.f;
-    if (lab != ignore)
-      l = (1.f - eps) * (lse - (float)x[lab]) + eps * (lse - SX / (float)Vv);
-    rowloss[row] = l / (float)max(1, nvalid[0]);
+    if (valid) l = (1.f - eps) * (lse - xl) + eps * (lse - SX / (float)Vv);
+    rowloss[row] = l / (float)max(1, n);
     lse_out[row] = lse;
   }
 }
 
 // grid (column blocks, rows): 8 columns per thread (V % 8 == 0) or 1
-template <class T, bool VEC>
+// the target of column col: eps / Vv + (1 - eps) on the label, or, pair-target, (1 - eps) times
+// lambda on label a plus 1 - lambda on label b
+template <bool MIX>
+__device__ __forceinline__ float ce_target(int col, int64_t lab, int64_t lab2, float lam,
+                                           float om, float base_t, float eps) {
+  if constexpr (MIX)
+    return base_t + (1.f - eps) * ((col == lab ? lam : 0.f) + (col == lab2 ? om : 0.f));
+  else
+    return base_t + (col == lab ? 1.f - eps : 0.f);
+}
+
+template <class T, bool VEC, bool MIX = false>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logits,
                                                      const int64_t* __restrict__ labels,
                                                      const float* __restrict__ lse,
                                                      const int* __restrict__ nvalid,
                                                      const float* __restrict__ gout,
                                                      T* __restrict__ grad, int R, int V, int Vv,
-                                                     float eps, int64_t ignore) {
+                                                     float eps, int64_t ignore,
+                                                     const float* __restrict__ mix = nullptr) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= (VEC ? V / 8 : V)) return;
-  const float gs = gout[0] / (float)max(1, nvalid[0]), base_t = eps / (float)Vv;
+  const float gs = gout[0] / (float)max(1, MIX ? R : nvalid[0]), base_t = eps / (float)Vv;
+  float lam = 1.f, om = 0.f;
+  if constexpr (MIX) {
+    lam = mix[0];
+    om = 1.f - lam;
+  }
   for (long row = blockIdx.y; row < R; row += gridDim.y) {  // (grid.y is capped at 65535)
   const int64_t lab = labels[row];
-  const float scale = lab != ignore ? gs : 0.f;
+  const int64_t lab2 = MIX ? labels[R - 1 - row] : lab;
+  const float scale = (MIX || lab != ignore) ? gs : 0.f;
   const float l = lse[row];
   if constexpr (VEC) {
     float v[8];
@@ -254,12 +292,12 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logit
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int col = c * 8 + q;
-      const float t = base_t + (col == lab ? 1.f - eps : 0.f);
+      const float t = ce_target<MIX>(col, lab, lab2, lam, om, base_t, eps);
       v[q] = col < Vv ? (__expf(v[q] - l) - t) * scale : 0.f;
     }
     store8(grad + row * V + c * 8, v);
   } else {
-    const float t = base_t + (c == lab ? 1.f - eps : 0.f);
+    const float t = ce_target<MIX>(c, lab, lab2, lam, om, base_t, eps);
     grad[row * V + c] = (T)(c < Vv ? (__expf((float)logits[row * V + c] - l) - t) * scale : 0.f);
   }
   }
@@ -293,6 +331,45 @@ void cross_entropy_bwd(const void* logits, const int64_t* labels, const int* wor
     hipLaunchKernelGGL((ce_bwd_kernel<T, decltype(vec_c)::value>), g, dim3(256), 0, st,
                        (const T*)logits, labels, lse, work, gout, (T*)grad, R, V, Vv,
                        smoothing, ignore_index);
+  };
+  if (f32) {
+    if (vec) go(float(), std::true_type());
+    else go(float(), std::false_type());
+  } else {
+    if (vec) go(__bf16(), std::true_type());
+    else go(__bf16(), std::false_type());
+  }
+}
+
+void cross_entropy_mixed_fwd(const void* logits, const int64_t* labels, const float* mix,
+                             float* loss, int R, int V, float smoothing, int* work,
+                             hipStream_t st, bool f32, int Vv) {
+  if (Vv <= 0 || Vv > V) Vv = V;
+  float* rowloss = reinterpret_cast<float*>(work + 4);
+  float* lse = rowloss + R;
+  if (f32)
+    hipLaunchKernelGGL((ce_fwd_kernel<float, true>), dim3(R), dim3(256), 0, st,
+                       (const float*)logits, labels, V, Vv, smoothing, (int64_t)0,
+                       (const int*)nullptr, rowloss, lse, mix);
+  else
+    hipLaunchKernelGGL((ce_fwd_kernel<__bf16, true>), dim3(R), dim3(256), 0, st,
+                       (const __bf16*)logits, labels, V, Vv, smoothing, (int64_t)0,
+                       (const int*)nullptr, rowloss, lse, mix);
+  hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(256), 0, st, rowloss, R, loss);
+}
+
+void cross_entropy_mixed_bwd(const void* logits, const int64_t* labels, const float* mix,
+                             const int* work, const float* gout, void* grad, int R, int V,
+                             float smoothing, hipStream_t st, bool f32, int Vv) {
+  if (Vv <= 0 || Vv > V) Vv = V;
+  const float* lse = reinterpret_cast<const float*>(work + 4) + R;
+  const bool vec = V % 8 == 0;
+  const dim3 g((unsigned)(((vec ? V / 8 : V) + 255) / 256), (unsigned)std::min(R, 65535));
+  auto go = [&](auto t, auto vec_c) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((ce_bwd_kernel<T, decltype(vec_c)::value, true>), g, dim3(256), 0, st,
+                       (const T*)logits, labels, lse, (const int*)nullptr, gout, (T*)grad, R, V,
+                       Vv, smoothing, (int64_t)0, mix);
   };
   if (f32) {
     if (vec) go(float(), std::true_type());

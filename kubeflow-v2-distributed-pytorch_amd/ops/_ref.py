@@ -231,6 +231,78 @@ def cross_entropy_fwd_bwd(logits: Tensor, labels: Tensor, label_smoothing: float
     return loss, grad.to(logits.dtype)
 
 
+def cross_entropy_mixed_fwd_bwd(logits: Tensor, labels: Tensor, mix: Tensor,
+                                label_smoothing: float = 0.0,
+                                valid_cols: int = -1) -> Tuple[Tensor, Tensor]:
+    """Pair-target CE (Mixup / CutMix) and its gradient wrt logits (for grad_output = 1).  Row
+    ``r`` of ``R`` has the labels ``a = labels[r]`` and ``b = labels[R-1-r]``; with ``lam =
+    mix[0]`` (the batch-mix descriptor, :mod:`mipipe.data.mix`) and ``eps = label_smoothing``
+    the target is ``t[c] = eps/Vv + (1-eps) * (lam*[c==a] + (1-lam)*[c==b])`` and the loss the
+    mean over all rows of ``lse - sum(t * x)``.  There is no ``ignore_index`` in this form: every
+    row counts.  ``valid_cols`` as in :func:`cross_entropy_fwd_bwd`."""
+    V = logits.shape[-1]
+    if 0 < valid_cols < V:
+        loss, g = cross_entropy_mixed_fwd_bwd(logits[:, :valid_cols], labels, mix,
+                                              label_smoothing)
+        return loss, torch.cat([g, g.new_zeros(g.shape[0], V - valid_cols)], 1)
+    lf = _f(logits)
+    R = lf.shape[0]
+    lam = mix.reshape(-1)[0].to(lf.dtype)
+    a = labels.long()
+    b = a.flip(0)
+    t = lam * F.one_hot(a, V).to(lf.dtype) + (1 - lam) * F.one_hot(b, V).to(lf.dtype)
+    t = t * (1 - label_smoothing) + label_smoothing / V
+    logp = torch.log_softmax(lf, dim=-1)
+    loss = -(t * logp).sum() / max(1, R)
+    grad = (logp.exp() - t) / max(1, R)
+    return loss, grad.to(logits.dtype)
+
+
+def batch_mix(x: Tensor, mix: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """Mixup / CutMix of ``x`` [B, C, H, W] (fp32 or bf16) with its own reverse — sample ``i`` is
+    paired with ``B-1-i`` — as the descriptor ``mix`` says (csrc/kernels/mix.hip's contract;
+    layout in :mod:`mipipe.data.mix`: ``[lam, mode, y0, y1, x0, x1, 0, 0]``).
+
+    * mode 0: ``out = x``; with ``out is x`` nothing is written.
+    * mode 1: ``out[i] = lam*x[i] + (1-lam)*x[B-1-i]`` in fp32: two rounded multiplies and one
+      rounded add, ``1-lam`` an fp32 subtraction, rounded once to ``x``'s type.
+    * mode 2: ``out[i] = x[B-1-i]`` inside the half-open box, ``x[i]`` outside.
+    * The middle sample of an odd batch is its own partner and keeps its bits in every mode
+      (``lam*a + (1-lam)*a`` is ``a``; the rounded sum would only be near it).
+
+    ``out``: ``x`` itself (in place), another tensor of the same shape and type, or None (new).
+    This reference reads the descriptor on the host; the kernel reads it on the device."""
+    B, C, H, W = x.shape
+    v = mix.reshape(-1)[:8].tolist()
+    mode = int(v[1]) if int(v[1]) in (1, 2) else 0
+    if mode == 0:
+        if out is None:
+            return x.clone()
+        if out is not x:
+            out.copy_(x)
+        return out
+    rev = x.flip(0)
+    if mode == 1:
+        lam = mix.reshape(-1)[0].float()
+        om = 1 - lam  # fp32
+        p = x.float() * lam
+        q = rev.float() * om
+        res = (p + q).to(x.dtype)
+        if B % 2:
+            res[B // 2] = x[B // 2]
+    else:
+        y0 = min(max(int(v[2]), 0), H)
+        y1 = min(max(int(v[3]), y0), H)
+        x0 = min(max(int(v[4]), 0), W)
+        x1 = min(max(int(v[5]), x0), W)
+        res = x.clone()
+        res[:, :, y0:y1, x0:x1] = rev[:, :, y0:y1, x0:x1]
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
 def sgd_step(param: Tensor, grad: Tensor, mom: Tensor, shadow: Optional[Tensor], lr: float,
              momentum: float, dampening: float, weight_decay: float, nesterov: bool,
              first_step: bool, grad_scale: float = 1.0) -> None:

@@ -8,8 +8,9 @@ backward, SGD step) decomposes into these units, each one or two HIP launches:
 * :func:`batchnorm_act` — BN normalize/affine + optional residual add (raw identity or a
   second BN'd branch) + ReLU in one pass; backward = one reduce pass + one apply pass that
   also produces the residual gradient;
-* :func:`linear`, :func:`cross_entropy`, :func:`max_pool2d`, :func:`global_avg_pool`,
-  :func:`layer_norm`, :func:`gelu`, :func:`attention`, :func:`embedding`.
+* :func:`linear`, :func:`cross_entropy`, :func:`cross_entropy_mixed` (the pair-target loss of
+  Mixup / CutMix), :func:`max_pool2d`, :func:`global_avg_pool`, :func:`layer_norm`,
+  :func:`gelu`, :func:`attention`, :func:`embedding`.
 
 Master weights stay fp32 (``nn.Parameter``); kernels consume a compute-dtype *shadow*
 (bf16 on the GPU) passed as a separate, non-differentiable argument; weight gradients come
@@ -1152,6 +1153,49 @@ def cross_entropy(logits: Tensor, labels: Tensor, label_smoothing: float = 0.0,
     """Fused log-softmax + NLL (mean) whose backward costs one scale.  ``valid_cols``: classes
     are the first columns only (tile-padded vocabulary)."""
     return _CrossEntropyFn.apply(logits, labels, label_smoothing, ignore_index, int(valid_cols))
+
+
+class _CrossEntropyMixedFn(Function):
+    """The split form of :class:`_CrossEntropyFn` with pair targets: lambda is read from the
+    device descriptor by the forward and by the backward, so a captured step follows it."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, mix, label_smoothing, valid_cols):
+        logits, labels = logits.contiguous(), labels.contiguous()
+        ctx.args = (label_smoothing, valid_cols)
+        ctx.split = K.use_native(logits)
+        if ctx.split:
+            loss, work = K.native().cross_entropy_mixed_fwd(logits, labels, mix, label_smoothing,
+                                                            valid_cols)
+            ctx.save_for_backward(logits, labels, mix, work)
+            return loss
+        loss, grad = K.cross_entropy_mixed_fwd_bwd(logits, labels, mix, label_smoothing,
+                                                   valid_cols)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.split:
+            logits, labels, mix, work = ctx.saved_tensors
+            gout = g.detach().reshape(1).to(torch.float32)
+            return (K.native().cross_entropy_mixed_bwd(logits, labels, mix, work, gout,
+                                                       *ctx.args),
+                    None, None, None, None)
+        (grad,) = ctx.saved_tensors
+        return (grad * g.to(grad.dtype)), None, None, None, None
+
+
+def cross_entropy_mixed(logits: Tensor, labels: Tensor, mix: Tensor, label_smoothing: float = 0.0,
+                        valid_cols: int = -1) -> Tensor:
+    """Cross-entropy (mean) of a Mixup / CutMix batch.  Row ``r`` of ``R`` carries the labels
+    ``labels[r]`` with weight ``mix[0]`` and ``labels[R-1-r]`` with weight ``1 - mix[0]``
+    (``mix``: the fp32[8] descriptor of :mod:`mipipe.data.mix` on the logits' device, read on the
+    device in forward and backward); contract: ``_ref.cross_entropy_mixed_fwd_bwd``.  No dense
+    target is built.  This form has no ``ignore_index``: every row counts.  With ``mix[0] == 1``
+    it gives the bits of :func:`cross_entropy`."""
+    return _CrossEntropyMixedFn.apply(logits, labels, mix, float(label_smoothing),
+                                      int(valid_cols))
 
 
 # ----------------------------------------------------------------------------- transformer ops

@@ -18,7 +18,8 @@ from ._native import native, native_available
 __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_wgrad", "bn_finalize", "bn_act_fwd",
            "bn_act_bwd_reduce", "bn_act_bwd_apply", "maxpool_fwd", "maxpool_bwd",
            "avgpool_fwd", "avgpool_bwd", "pool_bn_fwd", "pool_bn_bwd", "pool_bn_supported", "stem_fused_supported", "stem_fwd_stats",
-           "stem_fwd_pool", "stem_bwd", "gemm", "cross_entropy_fwd_bwd", "top1_correct", "sgd_step",
+           "stem_fwd_pool", "stem_bwd", "gemm", "cross_entropy_fwd_bwd", "cross_entropy_mixed_fwd_bwd",
+           "batch_mix", "top1_correct", "sgd_step",
            "adamw_step", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
            "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "record_decode", "record_decode_rrc",
            "use_native",
@@ -385,6 +386,29 @@ def cross_entropy_fwd_bwd(logits, labels, label_smoothing=0.0, ignore_index=-100
         return native().cross_entropy_fwd_bwd(logits, labels, label_smoothing, ignore_index,
                                               valid_cols)
     return _ref.cross_entropy_fwd_bwd(logits, labels, label_smoothing, ignore_index, valid_cols)
+
+
+def cross_entropy_mixed_fwd_bwd(logits, labels, mix, label_smoothing=0.0, valid_cols=-1):
+    """Pair-target CE (Mixup / CutMix; :func:`_ref.cross_entropy_mixed_fwd_bwd`'s contract) ->
+    (loss, gradient for an upstream gradient of 1)."""
+    if use_native(logits):
+        loss, work = native().cross_entropy_mixed_fwd(logits, labels, mix, label_smoothing,
+                                                      valid_cols)
+        one = torch.ones(1, dtype=torch.float32, device=logits.device)
+        return loss, native().cross_entropy_mixed_bwd(logits, labels, mix, work, one,
+                                                      label_smoothing, valid_cols)
+    return _ref.cross_entropy_mixed_fwd_bwd(logits, labels, mix, label_smoothing, valid_cols)
+
+
+def batch_mix(x, mix, out=None):
+    """Mixup / CutMix of ``x`` [B, C, H, W] (fp32 / bf16, contiguous) with its own reverse, as
+    the device-side descriptor ``mix`` (fp32[8], :mod:`mipipe.data.mix`) says; ``out``: ``x``
+    (in place), a tensor like ``x``, or None (new).  The kernel reads the descriptor on the
+    device: no host value enters the launch, so a captured step replays with the descriptor's
+    current contents."""
+    if use_native(x):
+        return native().batch_mix(x, mix, out)
+    return _ref.batch_mix(x, mix, out)
 
 
 def top1_correct(logits, labels, out=None):

@@ -33,6 +33,16 @@ the per-step values being device memory):
 ``--optimizer sgd`` with a schedule or clipping runs ``LARS(trust_coefficient=None)``: the same
 update as SGD with a device-side learning rate.  With a schedule active the step log line and
 ``metrics.json`` carry ``lr``.
+
+Regularisers (all off by default; :mod:`mipipe.data.mix`):
+  * ``--label-smoothing EPS``: the loss kernels' label smoothing;
+  * ``--mixup-alpha A`` / ``--cutmix-alpha A`` with ``--mix-prob`` and ``--mix-switch-prob``:
+    timm's batch-mode Mixup / CutMix.  Each training step builds its descriptor from
+    ``(random_seed, rank, epoch, step)``, mixes the batch with its own reverse in one kernel
+    (``batch_mix``) and takes the pair-target loss (``cross_entropy_mixed``); both read the
+    descriptor on the device, so the step stays capturable (``--hip-graph``: the descriptor is the
+    captured step's third input).  Evaluation is never mixed.  The step log line and
+    ``metrics.json`` carry ``mix_mode`` and ``mix_lambda``.
 """
 from __future__ import annotations
 
@@ -122,22 +132,24 @@ class CrossEntropyLoss(torch.nn.Module):
         self.label_smoothing = label_smoothing
         self.ignore_index = ignore_index
 
-    def _ce(self, logits, labels):
+    def _ce(self, logits, labels, mix=None):
+        if mix is not None:  # pair targets (Mixup / CutMix): every row counts, no ignore_index
+            return MF.cross_entropy_mixed(logits, labels, mix, self.label_smoothing)
         return MF.cross_entropy(logits, labels, self.label_smoothing, self.ignore_index)
 
-    def forward(self, logits, labels):
+    def forward(self, logits, labels, mix=None):
         if isinstance(logits, tuple) and hasattr(logits, "_fields"):
             # GoogLeNet / Inception-v3 in training mode return torchvision's named tuples
             # (main logits + auxiliary classifiers).  The reference hands them to
             # nn.CrossEntropyLoss (task.py:310) and crashes; here the auxiliary losses are added
             # with the papers' weights: 0.3 per GoogLeNet head, 0.4 for Inception-v3's.
             w = 0.4 if len(logits) == 2 else 0.3
-            loss = self._ce(logits[0], labels)
+            loss = self._ce(logits[0], labels, mix)
             for aux in logits[1:]:
                 if aux is not None:
-                    loss = loss + w * self._ce(aux, labels)
+                    loss = loss + w * self._ce(aux, labels, mix)
             return loss
-        return self._ce(logits, labels)
+        return self._ce(logits, labels, mix)
 
 
 def _unwrap(model):
@@ -200,6 +212,16 @@ def build_parser() -> argparse.ArgumentParser:
                    help="clip the global gradient norm to this value")
     p.add_argument("--trust-coefficient", type=float, default=0.001,
                    help="LARS trust coefficient")
+    p.add_argument("--label-smoothing", type=float, default=0.0,
+                   help="label smoothing of the training loss")
+    p.add_argument("--mixup-alpha", type=float, default=0.0,
+                   help="Mixup: lambda ~ Beta(a, a); 0 = off")
+    p.add_argument("--cutmix-alpha", type=float, default=0.0,
+                   help="CutMix: box area from lambda ~ Beta(a, a); 0 = off")
+    p.add_argument("--mix-prob", type=float, default=1.0,
+                   help="probability that a training step is mixed at all")
+    p.add_argument("--mix-switch-prob", type=float, default=0.5,
+                   help="probability of CutMix when both alphas are set")
     p.add_argument("--pretrained", dest="pretrained", action="store_true",
                    help="use pre-trained model: torchvision-format weights from "
                         "--pretrained-weights or the torchvision cache (no network download)")
@@ -418,7 +440,14 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                                         broadcast_buffers=not args.no_broadcast_buffers)
     elif use_gpu and args.gpu is None and _ngpus() > 1:
         model = DataParallel(model)  # task.py:201-208 path (d), on this replica's GPUs
-    criterion = CrossEntropyLoss().to(device)
+    criterion = CrossEntropyLoss(label_smoothing=args.label_smoothing).to(device)
+    mixer = None
+    if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
+        from mipipe.data.mix import BatchMixer
+        from mipipe.ops import kernels as MK
+        mixer = BatchMixer(args.random_seed, args.rank, device, mixup_alpha=args.mixup_alpha,
+                           cutmix_alpha=args.cutmix_alpha, prob=args.mix_prob,
+                           switch_prob=args.mix_switch_prob)
     optimizer = _make_optimizer(args, model.parameters(),
                                 compute_dtype if compute_dtype != torch.float32 else None)
     scheduled = not isinstance(optimizer, SGD) and (
@@ -509,9 +538,11 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
             print(f"=> --hip-graph off: {why}", flush=True)
             args.hip_graph = False
 
-    def _train_step(x, y):
+    def _train_step(x, y, mix=None):
         optimizer.zero_grad()
-        loss_ = criterion(model(x), y)
+        if mix is not None:
+            MK.batch_mix(x, mix, out=x)  # x is the captured step's own static buffer
+        loss_ = criterion(model(x), y, mix)
         loss_.backward()
         optimizer.step()
         return loss_
@@ -543,20 +574,26 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
             inputs, labels = batch
             _fault_check(args.rank, global_step)
             meter.step_begin()
+            extra = ()
+            if mixer is not None:  # one 32-byte upload; the kernels read it on the device
+                extra = (mixer.descriptor(epoch, i, inputs.shape[-2], inputs.shape[-1]),)
             if args.hip_graph and (graphed is None or tuple(inputs.shape) == graph_shape):
                 with trace.phase("graph_step"):
                     if graphed is None:
-                        graphed = GraphedStep(_train_step, (inputs, labels), warmup=1)
+                        graphed = GraphedStep(_train_step, (inputs, labels) + extra, warmup=1)
                         graph_shape = tuple(inputs.shape)
                         loss = graphed.warmup_loss  # the eager warm-up step trained this batch
                     else:
-                        loss = graphed.step(inputs, labels)
+                        loss = graphed.step(inputs, labels, *extra)
             else:
                 with trace.phase("zero_grad"):
                     optimizer.zero_grad()
                 with trace.phase("forward"):
+                    if mixer is not None:
+                        # out of place: the loader may yield this batch again (cached batches)
+                        inputs = MK.batch_mix(inputs.contiguous(), extra[0])
                     outputs = model(inputs)
-                    loss = criterion(outputs, labels)
+                    loss = criterion(outputs, labels, *extra)
                 with trace.phase("backward+allreduce"):
                     loss.backward()
                 with trace.phase("optimizer"):
@@ -570,10 +607,14 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                 last_loss = float(loss.detach().float().item())
                 # the LR the last step used, as its kernels computed it on the device
                 lr_kw = {"lr": float(optimizer.last_lr().item())} if scheduled else {}
+                if mixer is not None:
+                    lr_kw.update(mix_mode=mixer.last_mode, mix_lambda=mixer.last_lambda)
                 jlog.log("step", epoch=epoch, step=global_step, loss=last_loss,
                          samples_per_sec=meter.samples_per_sec(), **lr_kw)
                 if args.rank == 0:
                     lr_txt = f" lr {lr_kw['lr']:.6g}" if scheduled else ""
+                    if mixer is not None:
+                        lr_txt += f" mix {mixer.last_mode} lambda {mixer.last_lambda:.4f}"
                     print(f"epoch {epoch} step {global_step} loss {last_loss:.4f}{lr_txt} "
                           f"{meter.samples_per_sec() * world:.1f} samples/s (job)", flush=True)
         if args.rank == 0:
@@ -596,6 +637,8 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                "fused_eval": fused}
     if scheduled:
         metrics["lr"] = float(optimizer.last_lr().item())
+    if mixer is not None:
+        metrics.update(mix_mode=mixer.last_mode, mix_lambda=mixer.last_lambda)
     if args.rank == 0:
         ckpt.export_model(model, args, args.num_epochs, accuracy)
         ckpt.save_checkpoint(model, optimizer, args, args.num_epochs, best_acc1)
