@@ -1669,6 +1669,68 @@ void lamb_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> shadow, 
                            (float)eps, t.ratio, t.scal, t.t_dev, stream());
 }
 
+// ---- weight EMA (csrc/kernels/ema.hip)
+static void check_ema_args(const Tensor& t_dev, int64_t every, double w_min) {
+  check_cuda(t_dev, "calls_dev");
+  TORCH_CHECK(t_dev.scalar_type() == at::kInt && t_dev.numel() == 1, "calls_dev must be int32 [1]");
+  TORCH_CHECK(every >= 1 && every < (1ll << 31), "every must be >= 1");
+  TORCH_CHECK(w_min >= 0 && w_min <= 1, "w_min = 1 - decay must lie in [0, 1]");
+}
+
+// One call of the parameter average: e += w (p - e) when calls_dev % every == 0, else nothing.
+void ema_update(Tensor p, Tensor e, Tensor t_dev, int64_t every, double w_min, bool warmup,
+                Tensor scal) {
+  const int64_t n = p.numel();
+  TORCH_CHECK(n % 64 == 0, "flat buffer size must be a multiple of 64");
+  check_flat(p, n, "param");
+  check_flat(e, n, "ema");
+  TORCH_CHECK(p.data_ptr() != e.data_ptr(), "ema must not alias param");
+  check_ema_args(t_dev, every, w_min);
+  check_f32(scal, "scal");
+  TORCH_CHECK(scal.numel() >= 1, "scal must hold one float");
+  c10::DeviceGuard gd(p.device());
+  mipipe::ema_update(p.data_ptr<float>(), e.data_ptr<float>(), n, t_dev.data_ptr<int>(),
+                     (int)every, (float)w_min, warmup, scal.data_ptr<float>(), stream());
+}
+
+void ema_swap(Tensor p, Tensor e, optional<Tensor> shadow) {
+  const int64_t n = p.numel();
+  TORCH_CHECK(n % 64 == 0, "flat buffer size must be a multiple of 64");
+  check_flat(p, n, "param");
+  check_flat(e, n, "ema");
+  TORCH_CHECK(p.data_ptr() != e.data_ptr(), "ema must not alias param");
+  c10::DeviceGuard gd(p.device());
+  void* sh = optim_shadow(shadow, n);
+  TORCH_CHECK(sh == nullptr || reinterpret_cast<uintptr_t>(sh) % 8 == 0, "shadow must be 8-B aligned");
+  mipipe::ema_swap(p.data_ptr<float>(), e.data_ptr<float>(), sh, n, stream());
+}
+
+static int ema_table_rows(const Tensor& table, const Tensor& eb) {
+  check_cuda(table, "table");
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 3,
+              "table must be int64 [rows, 3]");
+  check_f32(eb, "ema buffers");
+  TORCH_CHECK(table.size(0) < (1ll << 31), "too many table rows");
+  return (int)table.size(0);
+}
+
+void ema_buffers_update(Tensor table, Tensor eb, Tensor t_dev, int64_t every, double w_min,
+                        bool warmup) {
+  const int rows = ema_table_rows(table, eb);
+  check_ema_args(t_dev, every, w_min);
+  c10::DeviceGuard gd(eb.device());
+  mipipe::ema_buffers_update((const long*)table.data_ptr<int64_t>(), rows, eb.data_ptr<float>(),
+                             eb.numel(), t_dev.data_ptr<int>(), (int)every, (float)w_min, warmup,
+                             stream());
+}
+
+void ema_buffers_swap(Tensor table, Tensor eb) {
+  const int rows = ema_table_rows(table, eb);
+  c10::DeviceGuard gd(eb.device());
+  mipipe::ema_buffers_swap((const long*)table.data_ptr<int64_t>(), rows, eb.data_ptr<float>(),
+                           eb.numel(), stream());
+}
+
 Tensor nchw_to_nhwc(Tensor x, at::ScalarType dtype, int64_t pad_to) {
   check_cuda(x, "x");
   c10::DeviceGuard g(x.device());
@@ -2469,6 +2531,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("kind"), py::arg("base_lr"), py::arg("end_lr"), py::arg("warmup"),
         py::arg("total"));
   m.attr("OPTIM_CHUNK") = mipipe::kOptimChunk;
+  m.def("ema_update", &ema_update, py::arg("p"), py::arg("ema"), py::arg("calls_dev"),
+        py::arg("every"), py::arg("w_min"), py::arg("warmup"), py::arg("scal"));
+  m.def("ema_swap", &ema_swap, py::arg("p"), py::arg("ema"), py::arg("shadow"));
+  m.def("ema_buffers_update", &ema_buffers_update, py::arg("table"), py::arg("ema_buffers"),
+        py::arg("calls_dev"), py::arg("every"), py::arg("w_min"), py::arg("warmup"));
+  m.def("ema_buffers_swap", &ema_buffers_swap, py::arg("table"), py::arg("ema_buffers"));
+  m.attr("EMA_ROW_MAX") = mipipe::kEmaRowMax;
   m.def("nchw_to_nhwc", &nchw_to_nhwc);
   m.def("synthetic_batch", &synthetic_batch);
   m.def("record_decode", &record_decode, py::arg("rec"), py::arg("idx"), py::arg("affine"),

@@ -427,6 +427,21 @@ void optim_lamb_apply(float* p, const float* m, const float* v, void* shadow, co
                       const int* segs, int nchunks, int nseg, long n, float lnb1, float lnb2,
                       float eps, const float* ratio, const float* scal, const int* t_dev,
                       hipStream_t st);
+// Weight EMA over the flat buffer (csrc/kernels/ema.hip); n a multiple of 64.  t_dev: the device
+// count of update() calls (already advanced).  A call with t % every != 0 touches no memory;
+// otherwise e += w (p - e) with w = warmup ? max(w_min, 9 / (10 + t / every - 1)) : w_min, and
+// scal[0] = w.
+void ema_update(const float* p, float* e, long n, const int* t_dev, int every, float w_min,
+                bool warmup, float* scal, hipStream_t st);
+// p' = e, e' = p, shadow' = bf16(p') (shadow may be null)
+void ema_swap(float* p, float* e, void* shadow, long n, hipStream_t st);
+// The same for small fp32 tensors outside the flat space.  table: int64 [nrows][3] = {source
+// address (4-byte aligned), offset into eb, length <= kEmaRowMax}; eb: the EMA's flat copy, nbuf
+// elements.  One block per row; a row that is out of range is ignored.
+constexpr int kEmaRowMax = 1024;
+void ema_buffers_update(const long* table, int nrows, float* eb, long nbuf, const int* t_dev,
+                        int every, float w_min, bool warmup, hipStream_t st);
+void ema_buffers_swap(const long* table, int nrows, float* eb, long nbuf, hipStream_t st);
 void nchw_to_nhwc(const void* x, bool x_is_bf16, void* y, int N, int C, int H, int W, int Cp,
                   hipStream_t st, bool y_f32 = false);
 // Stem "super-pixel" packing (C <= 4): y[n][h'][j][p*4 + c] = x[n][c][h'-pad][2j+p-pad] (zero

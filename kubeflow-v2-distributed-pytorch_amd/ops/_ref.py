@@ -409,6 +409,43 @@ def lamb_step(w: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, beta1: floa
     return r
 
 
+# ---- weight EMA: the contract of csrc/kernels/ema.hip
+
+def ema_weight(calls: int, every: int, w_min, warmup: bool):
+    """The averaging weight of ``update()`` call number ``calls`` (from 1) as an fp32 0-d tensor,
+    or None when the call is skipped (``calls % every != 0``).  ``u = calls/every − 1`` counts the
+    averaging updates from 0; ``w = max(w_min, 9/(10+u))`` with warm-up (timm's
+    ``1 − min(decay, (1+u)/(10+u))`` without the cancellation), else ``w_min``; all in fp32, with
+    ``w_min = float32(1 − decay)``."""
+    if every < 1 or calls < every or calls % every != 0:
+        return None
+    w = torch.tensor(float(w_min), dtype=torch.float32)
+    if warmup:
+        u = calls // every - 1
+        w = torch.maximum(w, torch.tensor(9.0, dtype=torch.float32)
+                          / torch.tensor(float(10 + u), dtype=torch.float32))
+    return w
+
+
+def ema_update(e: Tensor, p: Tensor, w) -> None:
+    """``e = e + w·(p − e)`` in place: a rounded subtract, a rounded multiply and a rounded add in
+    ``e``'s dtype, ``w`` an fp32 value (a float that fp32 holds exactly, or a 0-d tensor)."""
+    w = torch.as_tensor(w, dtype=torch.float32).to(device=e.device, dtype=e.dtype)
+    d = p - e
+    d.mul_(w)
+    e.add_(d)
+
+
+def ema_swap(p: Tensor, e: Tensor, shadow: Optional[Tensor] = None) -> None:
+    """``p' = e``, ``e' = p``, ``shadow' = p'`` rounded to the shadow's type: a pure exchange, so
+    two swaps restore all three tensors bit for bit."""
+    t = p.clone()
+    p.copy_(e)
+    e.copy_(t)
+    if shadow is not None:
+        shadow.copy_(p.to(shadow.dtype))
+
+
 def layernorm_fwd(x: Tensor, gamma: Tensor, beta: Tensor, eps: float,
                   residual: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
     """(y, mean, rstd, x_sum): y = LN(x [+ residual]); x_sum = x+residual (saved for bwd)."""

@@ -20,7 +20,8 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "avgpool_fwd", "avgpool_bwd", "pool_bn_fwd", "pool_bn_bwd", "pool_bn_supported", "stem_fused_supported", "stem_fwd_stats",
            "stem_fwd_pool", "stem_bwd", "gemm", "cross_entropy_fwd_bwd", "cross_entropy_mixed_fwd_bwd",
            "batch_mix", "top1_correct", "sgd_step",
-           "adamw_step", "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
+           "adamw_step", "ema_update", "ema_swap", "ema_buffers_update", "ema_buffers_swap",
+           "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
            "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "record_decode", "record_decode_rrc",
            "use_native",
            "gconv_fwd", "gconv_dgrad", "gconv_wgrad", "chan_stats", "affine_act",
@@ -443,6 +444,39 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, shadow, lr, beta1, beta2, eps, 
         step = int(step_dev.reshape(-1)[0].item())
     return _ref.adamw_step(param, grad, exp_avg, exp_avg_sq, shadow, lr, beta1, beta2, eps,
                            weight_decay, step, grad_scale)
+
+
+def ema_update(param, ema, calls_dev, every, w_min, warmup, scal):
+    """One ``update()`` call of the weight EMA over the flat buffer (csrc/kernels/ema.hip):
+    ``calls_dev`` (int32 [1], already advanced) decides on the device whether this call averages
+    (``calls % every == 0``) and with which weight (:func:`_ref.ema_weight`); then
+    ``ema += w·(param − ema)`` and ``scal[0] = w``.  A skipped call touches nothing."""
+    if use_native(param):
+        return native().ema_update(param, ema, calls_dev, int(every), float(w_min), bool(warmup),
+                                   scal)
+    w = _ref.ema_weight(int(calls_dev.reshape(-1)[0].item()), int(every), w_min, bool(warmup))
+    if w is not None:
+        _ref.ema_update(ema, param, w)
+        scal[0] = w
+
+
+def ema_swap(param, ema, shadow=None):
+    """Exchange the flat parameters and their average in place and rewrite the bf16 shadow."""
+    if use_native(param):
+        return native().ema_swap(param, ema, shadow)
+    return _ref.ema_swap(param, ema, shadow)
+
+
+def ema_buffers_update(table, ema_buffers, calls_dev, every, w_min, warmup):
+    """:func:`ema_update` for small fp32 tensors outside the flat space, reached through the
+    device ``table`` int64 [rows, 3] = (address, offset into ``ema_buffers``, length <= 1024).
+    GPU only: on the CPU :class:`mipipe.optim.ModelEMA` applies ``_ref`` per buffer."""
+    return native().ema_buffers_update(table, ema_buffers, calls_dev, int(every), float(w_min),
+                                       bool(warmup))
+
+
+def ema_buffers_swap(table, ema_buffers):
+    return native().ema_buffers_swap(table, ema_buffers)
 
 
 def layernorm_fwd(x, gamma, beta, eps, residual=None, drop=None):

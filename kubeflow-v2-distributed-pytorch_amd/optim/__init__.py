@@ -14,6 +14,9 @@ Both run ONE HIP kernel over the model's flat fp32 parameter buffer
 ``LARS`` / ``LAMB`` / ``LRSchedule`` (:mod:`mipipe.optim.large_batch`, ``csrc/kernels/optim.hip``)
 are the large-batch optimizers: layer-wise trust ratios, global-norm clipping and a learning-rate
 schedule whose per-step values all live on the device.
+
+``ModelEMA`` (:mod:`mipipe.optim.ema`, ``csrc/kernels/ema.hip``) averages the flat buffer and the
+BatchNorm statistics on the device and swaps the average under the model in place.
 """
 from __future__ import annotations
 
@@ -25,8 +28,8 @@ import torch
 from mipipe.ops import kernels as K
 from .flat import FlatParamSpace, get_flat_space, flat_space_for
 
-__all__ = ["SGD", "AdamW", "LARS", "LAMB", "LRSchedule", "FlatParamSpace", "get_flat_space",
-           "flat_space_for"]
+__all__ = ["SGD", "AdamW", "LARS", "LAMB", "LRSchedule", "ModelEMA", "FlatParamSpace",
+           "get_flat_space", "flat_space_for"]
 
 
 def _default_shadow_dtype(params: List[torch.Tensor]) -> Optional[torch.dtype]:
@@ -200,3 +203,4 @@ class AdamW(_FlatOptimizer):
 # large-batch training: LARS / LAMB with clipping and a device-side LR schedule (built on
 # _FlatOptimizer above, hence imported last)
 from .large_batch import LARS, LAMB, LRSchedule  # noqa: E402
+from .ema import ModelEMA  # noqa: E402

@@ -8,7 +8,9 @@
   the prefix (:func:`strip_module_prefix`).
 * ``save_checkpoint`` / ``load_checkpoint`` — the ImageNet-example format the reference's
   resume code expects (task.py:232-238): ``{'epoch','arch','best_acc1','state_dict',
-  'optimizer'}``, loaded with ``weights_only=True``.
+  'optimizer'}``, loaded with ``weights_only=True``.  With a weight EMA
+  (:class:`mipipe.optim.ModelEMA`) the checkpoint also holds ``'model_ema'`` and the export gains
+  a second file, ``<stem>_ema<ext>``, with the averaged weights under the same keys.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ import torch
 
 from mipipe.storage.gcs import uri_to_local_path
 
-__all__ = ["export_model", "save_checkpoint", "load_checkpoint", "load_model_state",
+__all__ = ["export_model", "ema_path", "save_checkpoint", "load_checkpoint", "load_model_state",
            "strip_module_prefix", "resolve_resume_path", "write_json", "CHECKPOINT_NAME"]
 
 CHECKPOINT_NAME = "checkpoint.pth.tar"
@@ -45,8 +47,31 @@ def _cpu_state_dict(model) -> Dict[str, torch.Tensor]:
     return {k: v.detach().to("cpu").clone() for k, v in model.state_dict().items()}
 
 
-def export_model(model, args, epoch: int, accuracy: Optional[float] = None) -> str:
+def ema_path(path: str) -> str:
+    """``<stem>_ema<ext>`` next to ``path``: the averaged model's export."""
+    stem, ext = os.path.splitext(path)
+    return f"{stem}_ema{ext}"
+
+
+def export_model(model, args, epoch: int, accuracy: Optional[float] = None, ema=None,
+                 accuracy_ema: Optional[float] = None) -> str:
+    """``ema`` (a :class:`mipipe.optim.ModelEMA`): the averaged model is saved as well, to
+    :func:`ema_path` of the live export, under the very keys of the live file."""
     sd = _cpu_state_dict(model)
+    path = _export_path(args)
+    _atomic_save(sd, path)
+    print(f"saved model (epoch {epoch}, accuracy {accuracy}) to {path}", flush=True)
+    if ema is not None:
+        avg = ema.module_state_dict()
+        prefix = "module." if any(k.startswith("module.") for k in sd) else ""
+        esd = {k: avg[k[len(prefix):]].to("cpu") for k in sd}
+        _atomic_save(esd, ema_path(path))
+        print(f"saved EMA model (epoch {epoch}, accuracy {accuracy_ema}) to {ema_path(path)}",
+              flush=True)
+    return path
+
+
+def _export_path(args) -> str:
     if args.local_training or not os.environ.get("AIP_MODEL_DIR"):
         base = args.model_dir or "."
         path = os.path.join(uri_to_local_path(base), args.model_filename)
@@ -55,8 +80,6 @@ def export_model(model, args, epoch: int, accuracy: Optional[float] = None) -> s
         parts = [base, "model", args.model_filename] if args.compat_nested_model_dir else \
             [base, args.model_filename]
         path = uri_to_local_path(os.path.join(*parts))
-    _atomic_save(sd, path)
-    print(f"saved model (epoch {epoch}, accuracy {accuracy}) to {path}", flush=True)
     return path
 
 
@@ -69,9 +92,13 @@ def _inner(model):
     return getattr(model, "module", model)
 
 
-def save_checkpoint(model, optimizer, args, epoch: int, best_acc1: float) -> str:
+def save_checkpoint(model, optimizer, args, epoch: int, best_acc1: float, ema=None) -> str:
     state = {"epoch": epoch, "arch": args.arch, "best_acc1": float(best_acc1),
              "state_dict": _cpu_state_dict(model), "optimizer": optimizer.state_dict()}
+    if ema is not None:  # mipipe.optim.ModelEMA: the averaged weights, call count and settings
+        esd = ema.state_dict()
+        esd["model"] = {k: v.to("cpu") for k, v in esd["model"].items()}
+        state["model_ema"] = esd
     step = getattr(_inner(model), "_step", None)
     if isinstance(step, int):
         # the model's dropout-seed step (BERT): a resumed run continues the mask sequence

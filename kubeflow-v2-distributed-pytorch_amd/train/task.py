@@ -43,6 +43,17 @@ Regularisers (all off by default; :mod:`mipipe.data.mix`):
     descriptor on the device, so the step stays capturable (``--hip-graph``: the descriptor is the
     captured step's third input).  Evaluation is never mixed.  The step log line and
     ``metrics.json`` carry ``mix_mode`` and ``mix_lambda``.
+
+Weight averaging (off by default; :class:`mipipe.optim.ModelEMA`):
+  * ``--model-ema-decay D`` (0 = off) with ``--model-ema-steps N`` (average every N-th step) and
+    ``--model-ema-warmup {0,1}`` (timm's ``min(D, (1+u)/(10+u))`` warm-up).  ``D`` is used as
+    given: torchvision's adjustment by batch size and epochs is the caller's to make.  The update
+    follows ``optimizer.step()`` and reads its call count on the device, so it is captured under
+    ``--hip-graph``.  Every evaluation runs twice, on the live model and with the average swapped
+    in place under the model: the printed line and ``metrics.json`` gain ``accuracy_ema`` and
+    ``ema_updates``, the export a second file ``<stem>_ema<ext>``, the checkpoint ``model_ema``.
+    ``--resume`` restores the average together with its call count and its decay / steps / warmup:
+    the checkpoint's settings replace the command line's (a line is printed when they differ).
 """
 from __future__ import annotations
 
@@ -222,6 +233,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="probability that a training step is mixed at all")
     p.add_argument("--mix-switch-prob", type=float, default=0.5,
                    help="probability of CutMix when both alphas are set")
+    p.add_argument("--model-ema-decay", type=float, default=0.0,
+                   help="decay of the exponential moving average of the weights, used as given "
+                        "(no batch-size adjustment); 0 = off. With --resume the checkpoint's "
+                        "decay / steps / warmup replace these flags")
+    p.add_argument("--model-ema-steps", type=int, default=1,
+                   help="average every N-th training step")
+    p.add_argument("--model-ema-warmup", type=int, choices=[0, 1], default=1,
+                   help="1: decay min(D, (1+u)/(10+u)) at averaging update u (timm's warm-up)")
     p.add_argument("--pretrained", dest="pretrained", action="store_true",
                    help="use pre-trained model: torchvision-format weights from "
                         "--pretrained-weights or the torchvision cache (no network download)")
@@ -452,6 +471,11 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                                 compute_dtype if compute_dtype != torch.float32 else None)
     scheduled = not isinstance(optimizer, SGD) and (
         args.lr_schedule != "constant" or args.lr_warmup_steps > 0)
+    ema = None
+    if args.model_ema_decay > 0:
+        from mipipe.optim import ModelEMA
+        ema = ModelEMA(model, decay=args.model_ema_decay, every=args.model_ema_steps,
+                       warmup=bool(args.model_ema_warmup))
 
     start_epoch = 0
     if args.resume:
@@ -464,6 +488,17 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
             ckpt.load_model_state(model, state["state_dict"])
             ckpt.restore_model_step(model, state)
             optimizer.load_state_dict(state["optimizer"])
+            if ema is not None:
+                if "model_ema" in state:
+                    asked = (ema.decay, ema.every, ema.warmup)
+                    ema.load_state_dict(state["model_ema"])
+                    # the average goes on as it was being taken: the checkpoint's settings win
+                    if asked != (ema.decay, ema.every, ema.warmup):
+                        print(f"=> model EMA: the checkpoint's decay / steps / warmup "
+                              f"{(ema.decay, ema.every, ema.warmup)} replace the command line's "
+                              f"{asked}", flush=True)
+                else:  # a run that had no EMA: the average starts from the loaded weights
+                    ema.reset()
             print(f"=> loaded checkpoint '{path}' (epoch {start_epoch})")
         else:
             print(f"=> no checkpoint found at '{path}'")
@@ -545,20 +580,34 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         loss_ = criterion(model(x), y, mix)
         loss_.backward()
         optimizer.step()
+        if ema is not None:
+            ema.update()
         return loss_
 
     fused = bool(args.fused_eval) or inference.is_fused_eval()
+
+    def _evaluate():
+        """(accuracy of the live model, accuracy of the averaged one or None)."""
+        with inference.fused_eval(fused):
+            acc = evaluate(model, device, test_loader)
+            if ema is None:
+                return acc, None
+            with ema.swapped():
+                return acc, evaluate(model, device, test_loader)
+
+    def _ema_txt(acc_ema):
+        return "" if ema is None else f", Accuracy EMA: {acc_ema} ({ema.num_updates()} updates)"
+
     for epoch in range(start_epoch, args.num_epochs):
         epoch_start = datetime.now().strftime("%Y_%m_%d_%H_%M_%S")
         print(f"Rank: {args.rank}, Epoch: {epoch}, Training start: {epoch_start}", flush=True)
         train_sampler.set_epoch(epoch)
         if epoch % args.eval_every == 0:
-            with inference.fused_eval(fused):
-                accuracy = evaluate(model, device, test_loader)
+            accuracy, accuracy_ema = _evaluate()
             if args.rank == 0:
-                ckpt.export_model(model, args, epoch, accuracy)
+                ckpt.export_model(model, args, epoch, accuracy, ema, accuracy_ema)
                 print("-" * 75)
-                print(f"Epoch: {epoch}, Accuracy: {accuracy}, Time: "
+                print(f"Epoch: {epoch}, Accuracy: {accuracy}{_ema_txt(accuracy_ema)}, Time: "
                       f"{datetime.now().strftime('%Y_%m_%d_%H_%M_%S')}")
                 print("-" * 75, flush=True)
         model.train()
@@ -598,6 +647,8 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                     loss.backward()
                 with trace.phase("optimizer"):
                     optimizer.step()
+                    if ema is not None:
+                        ema.update()
             meter.step_end(inputs.shape[0])
             global_step += 1
             i += 1
@@ -618,12 +669,11 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                     print(f"epoch {epoch} step {global_step} loss {last_loss:.4f}{lr_txt} "
                           f"{meter.samples_per_sec() * world:.1f} samples/s (job)", flush=True)
         if args.rank == 0:
-            ckpt.save_checkpoint(model, optimizer, args, epoch + 1, best_acc1)
+            ckpt.save_checkpoint(model, optimizer, args, epoch + 1, best_acc1, ema)
     if isinstance(model, DistributedDataParallel):
         model.check_comm_errors(final=True)
     # fixed quirk: evaluate and save the *trained* model at the end as well
-    with inference.fused_eval(fused):
-        accuracy = evaluate(model, device, test_loader)
+    accuracy, accuracy_ema = _evaluate()
     best_acc1 = max(best_acc1, accuracy)
     last_loss = float(loss.detach().float().item()) if global_step else last_loss
     metrics = {"accuracy": accuracy, "loss": last_loss, "epochs": args.num_epochs,
@@ -639,9 +689,11 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         metrics["lr"] = float(optimizer.last_lr().item())
     if mixer is not None:
         metrics.update(mix_mode=mixer.last_mode, mix_lambda=mixer.last_lambda)
+    if ema is not None:
+        metrics.update(accuracy_ema=accuracy_ema, ema_updates=ema.num_updates())
     if args.rank == 0:
-        ckpt.export_model(model, args, args.num_epochs, accuracy)
-        ckpt.save_checkpoint(model, optimizer, args, args.num_epochs, best_acc1)
+        ckpt.export_model(model, args, args.num_epochs, accuracy, ema, accuracy_ema)
+        ckpt.save_checkpoint(model, optimizer, args, args.num_epochs, best_acc1, ema)
         print("MIPIPE_METRICS " + json.dumps(metrics), flush=True)
         if args.metrics_file:
             ckpt.write_json(args.metrics_file, metrics)
