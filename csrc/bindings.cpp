@@ -1498,6 +1498,49 @@ Tensor top1_correct(Tensor logits, Tensor labels, optional<Tensor> out) {
   return o;
 }
 
+// Evaluation statistics of one batch (eval_stats.hip) accumulated into device buffers: counters
+// int64 [8], confusion int32 [Vv, Vv] (optional), hist int64 [3, bins] (optional, 1 <= bins <= 64).
+void eval_stats(Tensor logits, Tensor labels, Tensor counters, optional<Tensor> confusion,
+                optional<Tensor> hist, int64_t k, int64_t ignore_index, int64_t valid_cols) {
+  check_act(logits, "logits");
+  check_cuda(labels, "labels");
+  check_cuda(counters, "counters");
+  c10::DeviceGuard g(logits.device());
+  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
+  TORCH_CHECK(logits.dim() == 2 && labels.numel() == logits.size(0), "eval_stats shape mismatch");
+  TORCH_CHECK(labels.device() == logits.device(), "labels must be on the logits' device");
+  TORCH_CHECK(counters.scalar_type() == at::kLong && counters.numel() == 8 &&
+              counters.device() == logits.device(),
+              "counters must be int64 [8] on the logits' device");
+  const int64_t R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(R < (1ll << 31) - 4 && V < (1ll << 31), "eval_stats: logits too large");
+  const int64_t Vv = (valid_cols > 0 && valid_cols < V) ? valid_cols : V;
+  TORCH_CHECK(k >= 1 && k <= Vv, "k must be in [1, ", Vv, "], got ", k);
+  int* cm = nullptr;
+  if (confusion.has_value()) {
+    check_cuda(*confusion, "confusion");
+    TORCH_CHECK(confusion->scalar_type() == at::kInt && confusion->dim() == 2 &&
+                confusion->size(0) == Vv && confusion->size(1) == Vv &&
+                confusion->device() == logits.device(),
+                "confusion must be int32 [", Vv, ", ", Vv, "] on the logits' device");
+    cm = confusion->data_ptr<int>();
+  }
+  int64_t* hp = nullptr;
+  int64_t bins = 1;
+  if (hist.has_value()) {
+    check_cuda(*hist, "hist");
+    TORCH_CHECK(hist->scalar_type() == at::kLong && hist->dim() == 2 && hist->size(0) == 3 &&
+                hist->size(1) >= 1 && hist->size(1) <= 64 && hist->device() == logits.device(),
+                "hist must be int64 [3, bins] with 1 <= bins <= 64 on the logits' device");
+    bins = hist->size(1);
+    hp = hist->data_ptr<int64_t>();
+  }
+  if (R > 0)
+    mipipe::eval_stats(logits.data_ptr(), labels.data_ptr<int64_t>(), (int)R, (int)V, (int)Vv,
+                       (int)k, ignore_index, (int)bins, counters.data_ptr<int64_t>(), hp, cm,
+                       stream(), is_f32(logits));
+}
+
 void check_flat(const Tensor& t, int64_t n, const char* name) {
   check_f32(t, name);
   TORCH_CHECK(t.numel() == n, name, " size mismatch");
@@ -2581,6 +2624,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("stem_wgrad_unpack", &stem_wgrad_unpack, py::arg("dwp"), py::arg("g"));
   m.def("top1_correct", &top1_correct, py::arg("logits"), py::arg("labels"),
         py::arg("out") = py::none());
+  m.def("eval_stats", &eval_stats, py::arg("logits"), py::arg("labels"), py::arg("counters"),
+        py::arg("confusion") = py::none(), py::arg("hist") = py::none(), py::arg("k") = 5,
+        py::arg("ignore_index") = -100, py::arg("valid_cols") = -1);
   m.def("set_splitk_target", [](int v) { mipipe::g_splitk_target = std::max(1, v); });
   m.def("get_splitk_target", []() { return mipipe::g_splitk_target; });
   m.def("set_wgrad_xcd", [](bool on) { mipipe::g_wgrad_xcd = on ? 1 : 0; });

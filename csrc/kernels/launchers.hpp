@@ -374,6 +374,13 @@ void batch_mix(const void* x, void* out, const float* mix, int B, int C, int H, 
 // *correct += #rows whose first maximal logit is at the label (torch.argmax tie rule)
 void top1_correct(const void* logits, const int64_t* labels, int R, int V, int* correct,
                   hipStream_t st, bool f32 = false);
+// Evaluation statistics of logits [R, V] in one launch (eval_stats.hip): counters int64 [8] =
+// {rows, top1, topk, nonfinite, invalid, loss_q24, 0, 0}, hist int64 [3, bins] (wrong, correct,
+// Q24 confidence sum; may be null), cm int32 [Vv, Vv] (cm[label, pred]; may be null).  All are
+// accumulated with integer atomics.  Vv: the first Vv columns are classes; 1 <= k <= Vv.
+void eval_stats(const void* logits, const int64_t* labels, int R, int V, int Vv, int k,
+                int64_t ignore_index, int bins, int64_t* counters, int64_t* hist, int* cm,
+                hipStream_t st, bool f32);
 void sgd_step(float* p, const float* g, float* m, void* shadow, long n, float lr, float momentum,
               float dampening, float wd, bool nesterov, bool first, float grad_scale,
               hipStream_t st);

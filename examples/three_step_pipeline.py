@@ -158,16 +158,18 @@ def evaluate(data: Input[Dataset], model: Input[Model], arch: str, dataset: str,
                                   device=dev, label_bytes=int(man.get("label_bytes", 1)),
                                   decode="device" if dev.type == "cuda" and rkw else "host",
                                   **rkw)
-    cm = torch.zeros(ncls, ncls, dtype=torch.int64, device=dev)
+    from mipipe.metrics import EvalMeter
+    meter = EvalMeter(ncls, device=dev)  # one eval_stats launch per batch, one read at the end
     with torch.no_grad():
         for x, y in loader:
-            pred = net(x).float().argmax(1)
-            cm.index_put_((y, pred), torch.ones_like(y), accumulate=True)
-    cm = cm.cpu()
-    acc = 100.0 * float(cm.diag().sum()) / max(1, int(cm.sum()))
-    cats = [str(i) for i in range(ncls)]
-    metrics.log_confusion_matrix(cats, cm.tolist())
+            meter.update(net(x), y)
+    res = meter.log_to(metrics)  # confusion matrix + confidenceMetrics
+    hits = sum(row[i] for i, row in enumerate(res["confusion"]))
+    acc = 100.0 * float(hits) / max(1, res["rows"])
     summary.log_metric("accuracy", acc)
+    summary.log_metric("loss", res["loss"])
+    summary.log_metric(f"accuracy_top{meter.topk}", 100.0 * res[f"accuracy_top{meter.topk}"])
+    summary.log_metric("ece", res["ece"])
     summary.log_metric("baseline_accuracy", baseline_accuracy)
     deploy = "true" if acc >= baseline_accuracy else "false"
     summary.log_metric("deploy", 1.0 if deploy == "true" else 0.0)

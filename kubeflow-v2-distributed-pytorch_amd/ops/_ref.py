@@ -796,3 +796,76 @@ def record_decode_rrc(rec: Tensor, idx: Tensor, affine: Tensor, shape, out_size,
     x = v * affine[0].float().view(1, C, 1, 1)
     x = x + affine[1].float().view(1, C, 1, 1)
     return x.to(dtype), y
+
+
+EVAL_Q24 = float(1 << 24)  # fixed-point scale of the loss and confidence sums
+EVAL_LOSS_CAP = float(1 << 16)  # a row loss above this counts as non-finite
+
+
+def eval_stats(logits: Tensor, labels: Tensor, counters: Tensor,
+               confusion: Optional[Tensor] = None, hist: Optional[Tensor] = None, k: int = 5,
+               ignore_index: int = -100, valid_cols: int = -1) -> None:
+    """Evaluation statistics of logits ``[R, V]`` accumulated into integer buffers
+    (csrc/kernels/eval_stats.hip's contract).  ``Vv = valid_cols`` when ``0 < valid_cols < V``,
+    else ``V``: only the first ``Vv`` columns are classes, the rest enter no result.
+
+    * ``counters`` int64 [8] += ``[rows, top1, topk, nonfinite, invalid, loss_q24, 0, 0]``;
+    * ``confusion`` int32 ``[Vv, Vv]`` (optional): ``confusion[label, pred] += 1``;
+    * ``hist`` int64 ``[3, bins]`` (optional): row 0 counts wrong predictions per confidence
+      bin, row 1 correct ones, row 2 holds the Q24 sum of the confidences.
+
+    Per row with label ``y``: ``y == ignore_index`` skips the row entirely; ``y < 0`` or
+    ``y >= Vv`` counts it in ``invalid`` and nowhere else.  Logits are ordered with NaN above
+    every number and NaNs equal to each other.  ``pred`` is the first maximal index
+    (``torch.argmax``'s tie rule); ``rank = #{c: x[c] > x[y]} + #{c < y: x[c] == x[y]}``; the
+    row is a top-1 hit iff ``pred == y`` (``rank == 0``) and a top-k hit iff ``rank < k``.  The
+    loss ``logsumexp(x) - x[y]`` and the confidence ``exp(max - logsumexp)`` are fp32.  A row
+    whose loss is not finite or exceeds 2^16 counts in ``nonfinite`` and stays out of the loss sum
+    and the histogram (its top-k and confusion entries count); otherwise the loss, clamped at 0,
+    and the confidence are rounded to nearest into Q24 and added as integers.  The bin is
+    ``min(bins - 1, floor(conf * bins))``."""
+    R, V = logits.shape
+    Vv = valid_cols if 0 < valid_cols < V else V
+    if not 1 <= k <= Vv:
+        raise ValueError(f"k must be in [1, {Vv}], got {k}")
+    labels = labels.reshape(-1).long()
+    keep = labels != ignore_index
+    ok = keep & (labels >= 0) & (labels < Vv)
+    counters[4] += int((keep & ~ok).sum())
+    x = _f(logits[:, :Vv])[ok]
+    y = labels[ok]
+    n = x.shape[0]
+    if n == 0:
+        return
+    nan = x != x
+    has_nan = nan.any(1)
+    xy = x.gather(1, y[:, None])
+    nan_y = xy != xy
+    gt = (x > xy) | (nan & ~nan_y)
+    eq = (x == xy) | (nan & nan_y)
+    cols = torch.arange(Vv, device=x.device)
+    rank = gt.sum(1) + (eq & (cols[None, :] < y[:, None])).sum(1)
+    mx = torch.where(nan, torch.full_like(x, float("-inf")), x).max(1).values
+    is_max = torch.where(has_nan[:, None], nan, x == mx[:, None])
+    pred = is_max.to(torch.uint8).argmax(1)
+    hit = pred == y
+    lse = torch.logsumexp(x, 1)
+    loss = lse - xy[:, 0]
+    finite = torch.isfinite(loss) & (loss <= EVAL_LOSS_CAP)
+    loss_q = torch.round(loss[finite].clamp_min(0) * EVAL_Q24).to(torch.int64)
+    counters[0] += n
+    counters[1] += int(hit.sum())
+    counters[2] += int((rank < k).sum())
+    counters[3] += int((~finite).sum())
+    counters[5] += int(loss_q.sum())
+    if confusion is not None:
+        cm = torch.bincount(y * Vv + pred, minlength=Vv * Vv).reshape(Vv, Vv)
+        confusion += cm.to(confusion.dtype)
+    if hist is not None:
+        bins = hist.shape[1]
+        conf = torch.exp(mx - lse)[finite]
+        b = torch.floor(conf * bins).clamp(0, bins - 1).to(torch.int64)
+        h = hit[finite]
+        hist[0] += torch.bincount(b[~h], minlength=bins)
+        hist[1] += torch.bincount(b[h], minlength=bins)
+        hist[2].index_add_(0, b, torch.round(conf * EVAL_Q24).to(torch.int64))

@@ -19,7 +19,7 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "bn_act_bwd_reduce", "bn_act_bwd_apply", "maxpool_fwd", "maxpool_bwd",
            "avgpool_fwd", "avgpool_bwd", "pool_bn_fwd", "pool_bn_bwd", "pool_bn_supported", "stem_fused_supported", "stem_fwd_stats",
            "stem_fwd_pool", "stem_bwd", "gemm", "cross_entropy_fwd_bwd", "cross_entropy_mixed_fwd_bwd",
-           "batch_mix", "top1_correct", "sgd_step",
+           "batch_mix", "top1_correct", "eval_stats", "sgd_step",
            "adamw_step", "ema_update", "ema_swap", "ema_buffers_update", "ema_buffers_swap",
            "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
            "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "record_decode", "record_decode_rrc",
@@ -422,6 +422,21 @@ def top1_correct(logits, labels, out=None):
         return n
     out.add_(n)
     return out
+
+
+def eval_stats(logits, labels, counters, confusion=None, hist=None, k=5, ignore_index=-100,
+               valid_cols=-1):
+    """One batch of evaluation statistics accumulated into device buffers, one kernel, no host
+    sync (:func:`_ref.eval_stats` documents the contract): ``counters`` int64 [8] =
+    ``[rows, top1, topk, nonfinite, invalid, loss_q24, 0, 0]``, ``confusion`` int32 ``[Vv, Vv]``
+    (optional, ``confusion[label, pred]``), ``hist`` int64 ``[3, bins]`` (optional: wrong and
+    correct predictions per confidence bin, Q24 confidence sums)."""
+    if use_native(logits):
+        native().eval_stats(logits.contiguous(), labels.contiguous(), counters, confusion, hist,
+                            k, ignore_index, valid_cols)
+    else:
+        _ref.eval_stats(logits, labels, counters, confusion, hist, k, ignore_index, valid_cols)
+    return counters
 
 
 def sgd_step(param, grad, mom, shadow, lr, momentum, dampening, weight_decay, nesterov,

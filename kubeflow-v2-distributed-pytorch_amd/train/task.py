@@ -54,6 +54,16 @@ Weight averaging (off by default; :class:`mipipe.optim.ModelEMA`):
     ``ema_updates``, the export a second file ``<stem>_ema<ext>``, the checkpoint ``model_ema``.
     ``--resume`` restores the average together with its call count and its decay / steps / warmup:
     the checkpoint's settings replace the command line's (a line is printed when they differ).
+
+Evaluation metrics (:class:`mipipe.metrics.EvalMeter`, one ``eval_stats`` launch per batch):
+  * ``--eval-metrics {top1,full}`` (default ``top1``: the evaluation and the metrics as before).
+    ``full`` adds top-k accuracy (``--eval-topk K``, default 5), the validation loss, the expected
+    calibration error and, up to 4096 classes, the confusion matrix with macro-F1 and balanced
+    accuracy: the ``Accuracy:`` line gains the top-k accuracy and the loss, ``metrics.json`` gains
+    ``accuracy_top{k}``, ``eval_loss``, ``ece``, ``macro_f1`` and ``balanced_accuracy`` (with a
+    weight EMA the same keys suffixed ``_ema``).  ``accuracy`` is the same float in both modes.
+  * ``--eval-report PATH``: rank 0 writes the full result dict (confusion matrix, per-class
+    figures, confidence curve) of the last evaluation there.
 """
 from __future__ import annotations
 
@@ -193,6 +203,35 @@ def evaluate(model, device, test_loader) -> float:
     return float(t[0].item()) / max(1, int(t[1].item()))
 
 
+@torch.no_grad()
+def evaluate_full(model, device, test_loader, meter) -> dict:
+    """:func:`evaluate` with every metric of ``meter`` (:class:`mipipe.metrics.EvalMeter`): one
+    ``eval_stats`` launch per batch, sharded over ranks like :func:`evaluate`, summed with one
+    all-reduce and read back once.  Returns the meter's result dict; ``accuracy`` is the float
+    :func:`evaluate` returns."""
+    m = _unwrap(model)
+    was_training = m.training
+    m.eval()
+    meter.reset()
+    for images, labels in test_loader:
+        images, labels = images.to(device), labels.to(device)
+        meter.update(m(images), labels)
+    meter.all_reduce()
+    if was_training:
+        m.train()
+    return meter.result()
+
+
+# the keys of an EvalMeter result that --eval-metrics full adds to the run's metrics
+def _full_metrics(res: dict, topk: int, suffix: str = "") -> dict:
+    out = {f"accuracy_top{topk}{suffix}": res[f"accuracy_top{topk}"],
+           f"eval_loss{suffix}": res["loss"], f"ece{suffix}": res["ece"]}
+    for key in ("macro_f1", "balanced_accuracy"):
+        if key in res:
+            out[key + suffix] = res[key]
+    return out
+
+
 def build_parser() -> argparse.ArgumentParser:
     names = model_names()
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter,
@@ -293,6 +332,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--fused-eval", type=int, choices=[0, 1], default=0,
                    help="evaluate with BatchNorm, residual and ReLU fused into the conv epilogues "
                         "(mipipe.ops.inference; MIPIPE_FUSED_EVAL=1 turns it on as well)")
+    p.add_argument("--eval-metrics", choices=["top1", "full"], default="top1",
+                   help="top1: accuracy only; full: also top-k accuracy, loss, calibration error "
+                        "and (up to 4096 classes) the confusion matrix, from one kernel per batch")
+    p.add_argument("--eval-topk", type=int, default=5, help="k of the top-k accuracy (full)")
+    p.add_argument("--eval-report", default="",
+                   help="with --eval-metrics full: write the full result dict, confusion matrix "
+                        "included, to this JSON file (rank 0)")
     p.add_argument("--hip-graph", action="store_true",
                    help="replay full-size training steps (forward, backward with the DDP bucket "
                         "all-reduces, SGD) from one captured hipGraph; partial batches run eagerly")
@@ -586,14 +632,35 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
 
     fused = bool(args.fused_eval) or inference.is_fused_eval()
 
+    eval_meter = None
+    if args.eval_metrics == "full":
+        from mipipe.metrics import CONFUSION_MAX_CLASSES, EvalMeter
+        ncls = kw.get("num_classes", 1000)  # every model but mnist_cnn defaults to 1000 classes
+        eval_meter = EvalMeter(ncls, topk=args.eval_topk, confusion=ncls <= CONFUSION_MAX_CLASSES,
+                               device=device)
+    eval_full = {}  # the last evaluation's EvalMeter results: "" live model, "_ema" averaged
+
     def _evaluate():
         """(accuracy of the live model, accuracy of the averaged one or None)."""
         with inference.fused_eval(fused):
+            if eval_meter is not None:
+                eval_full[""] = evaluate_full(model, device, test_loader, eval_meter)
+                if ema is None:
+                    return eval_full[""]["accuracy"], None
+                with ema.swapped():
+                    eval_full["_ema"] = evaluate_full(model, device, test_loader, eval_meter)
+                return eval_full[""]["accuracy"], eval_full["_ema"]["accuracy"]
             acc = evaluate(model, device, test_loader)
             if ema is None:
                 return acc, None
             with ema.swapped():
                 return acc, evaluate(model, device, test_loader)
+
+    def _full_txt():
+        if eval_meter is None:
+            return ""
+        k, res = eval_meter.topk, eval_full[""]
+        return f", Top-{k}: {res[f'accuracy_top{k}']}, Loss: {res['loss']:.4f}"
 
     def _ema_txt(acc_ema):
         return "" if ema is None else f", Accuracy EMA: {acc_ema} ({ema.num_updates()} updates)"
@@ -607,7 +674,7 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
             if args.rank == 0:
                 ckpt.export_model(model, args, epoch, accuracy, ema, accuracy_ema)
                 print("-" * 75)
-                print(f"Epoch: {epoch}, Accuracy: {accuracy}{_ema_txt(accuracy_ema)}, Time: "
+                print(f"Epoch: {epoch}, Accuracy: {accuracy}{_full_txt()}{_ema_txt(accuracy_ema)}, Time: "
                       f"{datetime.now().strftime('%Y_%m_%d_%H_%M_%S')}")
                 print("-" * 75, flush=True)
         model.train()
@@ -691,6 +758,12 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         metrics.update(mix_mode=mixer.last_mode, mix_lambda=mixer.last_lambda)
     if ema is not None:
         metrics.update(accuracy_ema=accuracy_ema, ema_updates=ema.num_updates())
+    if eval_meter is not None:
+        for suffix, res in eval_full.items():
+            metrics.update(_full_metrics(res, eval_meter.topk, suffix))
+        if args.rank == 0 and args.eval_report:
+            ckpt.write_json(args.eval_report, eval_full[""] if ema is None else
+                            {**eval_full[""], "ema": eval_full["_ema"]})
     if args.rank == 0:
         ckpt.export_model(model, args, args.num_epochs, accuracy, ema, accuracy_ema)
         ckpt.save_checkpoint(model, optimizer, args, args.num_epochs, best_acc1, ema)
