@@ -1541,31 +1541,53 @@ void eval_stats(Tensor logits, Tensor labels, Tensor counters, optional<Tensor> 
                        stream(), is_f32(logits));
 }
 
-void check_flat(const Tensor& t, int64_t n, const char* name) {
-  check_f32(t, name);
-  TORCH_CHECK(t.numel() == n, name, " size mismatch");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-B aligned");
+// ---- flat-buffer kernels (csrc/kernels/optim.hip, ema.hip): the argument checks they share
+// p and every named state tensor: fp32, contiguous, on the GPU, p's size (a multiple of `align`),
+// 16-B aligned.  Returns the size.
+struct FlatArg {
+  const Tensor& t;
+  const char* name;
+};
+static int64_t flat_n(const Tensor& p, int64_t align, std::initializer_list<FlatArg> state) {
+  const int64_t n = p.numel();
+  TORCH_CHECK(n % align == 0, "flat buffer size must be a multiple of ", align);
+  auto check = [n](const Tensor& t, const char* name) {
+    check_f32(t, name);
+    TORCH_CHECK(t.numel() == n, name, " size mismatch");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-B aligned");
+  };
+  check(p, "param");
+  for (const FlatArg& a : state) check(a.t, a.name);
+  return n;
+}
+
+// The bf16 shadow of the flat parameters (optional), written with 8-byte stores.
+static void* flat_shadow(const optional<Tensor>& shadow, int64_t n) {
+  if (!shadow.has_value()) return nullptr;
+  check_cuda(*shadow, "shadow");
+  TORCH_CHECK(shadow->numel() == n && shadow->scalar_type() == at::kBFloat16, "shadow mismatch");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(shadow->data_ptr()) % 8 == 0, "shadow must be 8-B aligned");
+  return shadow->data_ptr();
+}
+
+// A per-step count that lives on the device: int32 [1].
+static const int* dev_counter(const Tensor& t, const char* name) {
+  check_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kInt && t.numel() == 1, name, " must be int32 [1]");
+  return t.data_ptr<int>();
 }
 
 void sgd_step(Tensor p, Tensor g, Tensor m, optional<Tensor> shadow, double lr, double momentum,
               double dampening, double wd, bool nesterov, bool first, double grad_scale) {
-  int64_t n = p.numel();
-  TORCH_CHECK(n % 4 == 0, "flat buffer size must be a multiple of 4");
-  check_flat(p, n, "param");
-  check_flat(g, n, "grad");
-  check_flat(m, n, "momentum");
+  const int64_t n = flat_n(p, 4, {{g, "grad"}, {m, "momentum"}});
   c10::DeviceGuard gd(p.device());
-  void* sh = nullptr;
-  if (shadow.has_value()) {
-    check_cuda(*shadow, "shadow");
-    TORCH_CHECK(shadow->numel() == n && shadow->scalar_type() == at::kBFloat16, "shadow mismatch");
-    sh = shadow->data_ptr();
-  }
+  void* sh = flat_shadow(shadow, n);
   mipipe::sgd_step(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), sh, n, (float)lr,
                    (float)momentum, (float)dampening, (float)wd, nesterov, first,
                    (float)grad_scale, stream());
 }
 
+// an optional device word mixed into a dropout seed (the transformer ops below)
 static const int* i32_dev(const optional<Tensor>& t, const char* name) {
   if (!t.has_value()) return nullptr;
   check_cuda(*t, name);
@@ -1576,23 +1598,14 @@ static const int* i32_dev(const optional<Tensor>& t, const char* name) {
 void adamw_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> shadow, double lr,
                 double b1, double b2, double eps, double wd, int64_t step, double grad_scale,
                 optional<Tensor> step_dev) {
-  int64_t n = p.numel();
-  TORCH_CHECK(n % 4 == 0, "flat buffer size must be a multiple of 4");
-  check_flat(p, n, "param");
-  check_flat(g, n, "grad");
-  check_flat(m, n, "exp_avg");
-  check_flat(v, n, "exp_avg_sq");
+  const int64_t n = flat_n(p, 4, {{g, "grad"}, {m, "exp_avg"}, {v, "exp_avg_sq"}});
   c10::DeviceGuard gd(p.device());
-  void* sh = nullptr;
-  if (shadow.has_value()) {
-    TORCH_CHECK(shadow->numel() == n && shadow->scalar_type() == at::kBFloat16, "shadow mismatch");
-    sh = shadow->data_ptr();
-  }
+  void* sh = flat_shadow(shadow, n);
   double bc1 = 1.0 - std::pow(b1, (double)step), bc2 = 1.0 - std::pow(b2, (double)step);
   mipipe::adamw_step(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
                      v.data_ptr<float>(), sh, n, (float)lr, (float)b1, (float)b2, (float)eps,
                      (float)wd, (float)bc1, (float)bc2, (float)grad_scale, stream(),
-                     i32_dev(step_dev, "step_dev"));
+                     step_dev.has_value() ? dev_counter(*step_dev, "step_dev") : nullptr);
 }
 
 // ---- LARS / LAMB (csrc/kernels/optim.hip): the optimizer's device tables, checked per call
@@ -1621,23 +1634,14 @@ static OptimTabs optim_tabs(const Tensor& chunks, const Tensor& segs, const Tens
   check_vec(segtot, 2 * (int64_t)o.nseg, "segtot");
   check_vec(ratio, o.nseg, "ratio");
   check_vec(scal, 4, "scal");
-  check_cuda(t_dev, "step_dev");
-  TORCH_CHECK(t_dev.scalar_type() == at::kInt && t_dev.numel() == 1, "step_dev must be int32 [1]");
   o.chunks = chunks.data_ptr<int>();
   o.segs = segs.data_ptr<int>();
   o.part = part.data_ptr<float>();
   o.segtot = segtot.data_ptr<float>();
   o.ratio = ratio.data_ptr<float>();
   o.scal = scal.data_ptr<float>();
-  o.t_dev = t_dev.data_ptr<int>();
+  o.t_dev = dev_counter(t_dev, "step_dev");
   return o;
-}
-
-static void* optim_shadow(const optional<Tensor>& shadow, int64_t n) {
-  if (!shadow.has_value()) return nullptr;
-  check_cuda(*shadow, "shadow");
-  TORCH_CHECK(shadow->numel() == n && shadow->scalar_type() == at::kBFloat16, "shadow mismatch");
-  return shadow->data_ptr();
 }
 
 static mipipe::OptimSched optim_sched(int64_t kind, double base, double end, int64_t warmup,
@@ -1654,13 +1658,9 @@ void lars_step(Tensor p, Tensor g, Tensor m, optional<Tensor> shadow, Tensor chu
                Tensor part, Tensor segtot, Tensor ratio, Tensor scal, Tensor step_dev,
                double momentum, double tc, double eps, double max_norm, double grad_scale,
                int64_t kind, double base_lr, double end_lr, int64_t warmup, int64_t total) {
-  const int64_t n = p.numel();
-  TORCH_CHECK(n % 64 == 0, "flat buffer size must be a multiple of 64");
-  check_flat(p, n, "param");
-  check_flat(g, n, "grad");
-  check_flat(m, n, "momentum");
+  const int64_t n = flat_n(p, 64, {{g, "grad"}, {m, "momentum"}});
   c10::DeviceGuard gd(p.device());
-  void* sh = optim_shadow(shadow, n);
+  void* sh = flat_shadow(shadow, n);
   const OptimTabs t = optim_tabs(chunks, segs, part, segtot, ratio, scal, step_dev);
   const auto sc = optim_sched(kind, base_lr, end_lr, warmup, total);
   const bool norms = tc >= 0 || max_norm > 0;
@@ -1681,15 +1681,10 @@ void lamb_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> shadow, 
                Tensor step_dev, double b1, double b2, double eps, double max_norm,
                double grad_scale, int64_t kind, double base_lr, double end_lr, int64_t warmup,
                int64_t total) {
-  const int64_t n = p.numel();
-  TORCH_CHECK(n % 64 == 0, "flat buffer size must be a multiple of 64");
   TORCH_CHECK(b1 > 0 && b1 < 1 && b2 > 0 && b2 < 1, "LAMB betas must lie in (0, 1)");
-  check_flat(p, n, "param");
-  check_flat(g, n, "grad");
-  check_flat(m, n, "exp_avg");
-  check_flat(v, n, "exp_avg_sq");
+  const int64_t n = flat_n(p, 64, {{g, "grad"}, {m, "exp_avg"}, {v, "exp_avg_sq"}});
   c10::DeviceGuard gd(p.device());
-  void* sh = optim_shadow(shadow, n);
+  void* sh = flat_shadow(shadow, n);
   const OptimTabs t = optim_tabs(chunks, segs, part, segtot, ratio, scal, step_dev);
   const auto sc = optim_sched(kind, base_lr, end_lr, warmup, total);
   float *pp = p.data_ptr<float>(), *gp = g.data_ptr<float>();
@@ -1713,38 +1708,31 @@ void lamb_step(Tensor p, Tensor g, Tensor m, Tensor v, optional<Tensor> shadow, 
 }
 
 // ---- weight EMA (csrc/kernels/ema.hip)
-static void check_ema_args(const Tensor& t_dev, int64_t every, double w_min) {
-  check_cuda(t_dev, "calls_dev");
-  TORCH_CHECK(t_dev.scalar_type() == at::kInt && t_dev.numel() == 1, "calls_dev must be int32 [1]");
+static const int* check_ema_args(const Tensor& t_dev, int64_t every, double w_min) {
+  const int* t = dev_counter(t_dev, "calls_dev");
   TORCH_CHECK(every >= 1 && every < (1ll << 31), "every must be >= 1");
   TORCH_CHECK(w_min >= 0 && w_min <= 1, "w_min = 1 - decay must lie in [0, 1]");
+  return t;
 }
 
 // One call of the parameter average: e += w (p - e) when calls_dev % every == 0, else nothing.
 void ema_update(Tensor p, Tensor e, Tensor t_dev, int64_t every, double w_min, bool warmup,
                 Tensor scal) {
-  const int64_t n = p.numel();
-  TORCH_CHECK(n % 64 == 0, "flat buffer size must be a multiple of 64");
-  check_flat(p, n, "param");
-  check_flat(e, n, "ema");
+  const int64_t n = flat_n(p, 64, {{e, "ema"}});
   TORCH_CHECK(p.data_ptr() != e.data_ptr(), "ema must not alias param");
-  check_ema_args(t_dev, every, w_min);
+  const int* t = check_ema_args(t_dev, every, w_min);
   check_f32(scal, "scal");
   TORCH_CHECK(scal.numel() >= 1, "scal must hold one float");
   c10::DeviceGuard gd(p.device());
-  mipipe::ema_update(p.data_ptr<float>(), e.data_ptr<float>(), n, t_dev.data_ptr<int>(),
+  mipipe::ema_update(p.data_ptr<float>(), e.data_ptr<float>(), n, t,
                      (int)every, (float)w_min, warmup, scal.data_ptr<float>(), stream());
 }
 
 void ema_swap(Tensor p, Tensor e, optional<Tensor> shadow) {
-  const int64_t n = p.numel();
-  TORCH_CHECK(n % 64 == 0, "flat buffer size must be a multiple of 64");
-  check_flat(p, n, "param");
-  check_flat(e, n, "ema");
+  const int64_t n = flat_n(p, 64, {{e, "ema"}});
   TORCH_CHECK(p.data_ptr() != e.data_ptr(), "ema must not alias param");
   c10::DeviceGuard gd(p.device());
-  void* sh = optim_shadow(shadow, n);
-  TORCH_CHECK(sh == nullptr || reinterpret_cast<uintptr_t>(sh) % 8 == 0, "shadow must be 8-B aligned");
+  void* sh = flat_shadow(shadow, n);
   mipipe::ema_swap(p.data_ptr<float>(), e.data_ptr<float>(), sh, n, stream());
 }
 
@@ -1760,11 +1748,10 @@ static int ema_table_rows(const Tensor& table, const Tensor& eb) {
 void ema_buffers_update(Tensor table, Tensor eb, Tensor t_dev, int64_t every, double w_min,
                         bool warmup) {
   const int rows = ema_table_rows(table, eb);
-  check_ema_args(t_dev, every, w_min);
+  const int* t = check_ema_args(t_dev, every, w_min);
   c10::DeviceGuard gd(eb.device());
   mipipe::ema_buffers_update((const long*)table.data_ptr<int64_t>(), rows, eb.data_ptr<float>(),
-                             eb.numel(), t_dev.data_ptr<int>(), (int)every, (float)w_min, warmup,
-                             stream());
+                             eb.numel(), t, (int)every, (float)w_min, warmup, stream());
 }
 
 void ema_buffers_swap(Tensor table, Tensor eb) {

@@ -343,7 +343,7 @@ void pool_bn_bwd_apply(const void* dp, const uint8_t* idx, const void* pout, con
 void avgpool_fwd(const void* x, void* y, int N, int HW, int C, hipStream_t st, bool f32 = false);
 void avgpool_bwd(const void* dy, void* dx, int N, int HW, int C, hipStream_t st, bool f32 = false);
 
-// ---- loss / optimizer / data -----------------------------------------------------------------
+// ---- loss / data ------------------------------------------------------------------------------
 // work: 4 ints (valid-row count) then R floats (per-row losses, summed in a fixed order: the
 // loss is bit-reproducible)
 void cross_entropy_fwd_bwd(const void* logits, const int64_t* labels, float* loss, void* grad,
@@ -381,9 +381,6 @@ void top1_correct(const void* logits, const int64_t* labels, int R, int V, int* 
 void eval_stats(const void* logits, const int64_t* labels, int R, int V, int Vv, int k,
                 int64_t ignore_index, int bins, int64_t* counters, int64_t* hist, int* cm,
                 hipStream_t st, bool f32);
-void sgd_step(float* p, const float* g, float* m, void* shadow, long n, float lr, float momentum,
-              float dampening, float wd, bool nesterov, bool first, float grad_scale,
-              hipStream_t st);
 // One-shot collective over peer workspaces (csrc/kernels/oneshot.hip): fp32 sum * scale
 // (reduce) or a byte broadcast from `src`; nbytes % 16 == 0, nbytes <= cap.  nblocks: the
 // communicator's fixed grid (oneshot_blocks(cap)); timeout_s: the bounded wait for a peer.
@@ -396,6 +393,14 @@ void oneshot_launch(char* const* bases, int rank, int world, const void* in, voi
 // DDP bf16 wire: wire = bf16(g * scale), g = fp32(wire); n % 8 == 0, 16-B aligned pointers
 void grad_pack_bf16(const float* g, void* wire, long n, float scale, hipStream_t st);
 void grad_unpack_bf16(const void* wire, float* g, long n, hipStream_t st);
+
+// ---- flat fp32 parameter buffer: optimizers (optim.hip) and weight EMA (ema.hip) --------------
+// Every kernel here streams over p and its state through flat_access.hpp; bit 1024 of g_nt_store
+// makes the fp32 accesses non-temporal.  shadow (may be null): the bf16 copy of p, 8-B aligned.
+// SGD-momentum and AdamW: one launch, n % 4 == 0.
+void sgd_step(float* p, const float* g, float* m, void* shadow, long n, float lr, float momentum,
+              float dampening, float wd, bool nesterov, bool first, float grad_scale,
+              hipStream_t st);
 // t_dev (device step counter, may be null): bias corrections 1 - b^t computed in the kernel
 void adamw_step(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr,
                 float b1, float b2, float eps, float wd, float bc1, float bc2, float grad_scale,
@@ -449,6 +454,8 @@ constexpr int kEmaRowMax = 1024;
 void ema_buffers_update(const long* table, int nrows, float* eb, long nbuf, const int* t_dev,
                         int every, float w_min, bool warmup, hipStream_t st);
 void ema_buffers_swap(const long* table, int nrows, float* eb, long nbuf, hipStream_t st);
+
+// ---- input layout, stem, synthetic data and record decode --------------------------------------
 void nchw_to_nhwc(const void* x, bool x_is_bf16, void* y, int N, int C, int H, int W, int Cp,
                   hipStream_t st, bool y_f32 = false);
 // Stem "super-pixel" packing (C <= 4): y[n][h'][j][p*4 + c] = x[n][c][h'-pad][2j+p-pad] (zero

@@ -1,8 +1,7 @@
 // Memory-bound kernels of the training step: fused cross-entropy (fwd+bwd in one pass over
-// the logits), flat-buffer SGD-momentum / AdamW (one launch for the whole model, also emitting
-// the bf16 weight shadow), NCHW->NHWC input conversion, on-device synthetic data, GELU,
-// LayerNorm, embedding-grad scatter and column sums.  16-B vector accesses throughout
-// (cdna_hip_programming.md Guideline 13).
+// the logits), the DDP bf16 gradient wire, NCHW->NHWC input conversion, on-device synthetic data,
+// GELU, LayerNorm, embedding-grad scatter and column sums.  16-B vector accesses throughout
+// (cdna_hip_programming.md Guideline 13).  The optimizers live in optim.hip.
 #include "common.hpp"
 #include "launchers.hpp"
 
@@ -457,48 +456,6 @@ void top1_correct(const void* logits, const int64_t* labels, int R, int V, int* 
     hipLaunchKernelGGL(top1_correct_kernel<__bf16>, g, dim3(256), 0, st, (const __bf16*)logits, labels, R, V, correct);
 }
 
-// ------------------------------------------------------------------------------ optimizers
-// SGD ([torch] optim/sgd.py:354-380): g += wd*p; m = momentum*m + (1-damp)*g (m = g first);
-// p -= lr * (nesterov ? g + momentum*m : m).  Flat fp32 buffers, n % 4 == 0.
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                  float* __restrict__ m, __bf16* __restrict__ sh,
-                                                  long n4, float lr, float mom, float damp, float wd,
-                                                  bool nesterov, bool first, float gs) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (long)gridDim.x * blockDim.x) {
-    float4 pv = reinterpret_cast<float4*>(p)[i];
-    float4 gv = reinterpret_cast<const float4*>(g)[i];
-    float pa[4] = {pv.x, pv.y, pv.z, pv.w};
-    float ga[4] = {gv.x * gs, gv.y * gs, gv.z * gs, gv.w * gs};
-    if (mom != 0.f) {
-      float4 mv = reinterpret_cast<float4*>(m)[i];
-      float ma[4] = {mv.x, mv.y, mv.z, mv.w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float d = ga[q] + wd * pa[q];
-        ma[q] = first ? d : mom * ma[q] + (1.f - damp) * d;
-        float upd = nesterov ? d + mom * ma[q] : ma[q];
-        pa[q] -= lr * upd;
-      }
-      reinterpret_cast<float4*>(m)[i] = make_float4(ma[0], ma[1], ma[2], ma[3]);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) pa[q] -= lr * (ga[q] + wd * pa[q]);
-    }
-    reinterpret_cast<float4*>(p)[i] = make_float4(pa[0], pa[1], pa[2], pa[3]);
-    if (sh != nullptr)
-      reinterpret_cast<uint2*>(sh)[i] = make_uint2(pack2(pa[0], pa[1]), pack2(pa[2], pa[3]));
-  }
-}
-
-void sgd_step(float* p, const float* g, float* m, void* shadow, long n, float lr, float momentum,
-              float dampening, float wd, bool nesterov, bool first, float grad_scale,
-              hipStream_t st) {
-  long n4 = n / 4;
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid1d(n4, 4)), dim3(256), 0, st, p, g, m, (__bf16*)shadow,
-                     n4, lr, momentum, dampening, wd, nesterov, first, grad_scale);
-}
-
 // ------------------------------------------------------------------------------ DDP wire format
 // bf16 gradient wire (DistributedDataParallel(comm_dtype=bf16)): one pass turns a
 // bucket of the flat fp32 gradient into bf16 already multiplied by 1/world, so RCCL's SUM is the
@@ -541,116 +498,6 @@ void grad_unpack_bf16(const void* wire, float* g, long n, hipStream_t st) {
   if (n8 == 0) return;
   hipLaunchKernelGGL(grad_unpack_bf16_kernel, dim3(grid1d(n8, 4)), dim3(256), 0, st,
                      (const uint4*)wire, g, n8);
-}
-
-// NT: streaming (non-temporal) loads / stores of the fp32 state (p, g, m, v: 16 B per parameter
-// each, touched once per step); the bf16 shadow the next forward reads stays cached
-template <bool NT>
-__device__ __forceinline__ float4 ldf4(const float* p, long i) {
-  if constexpr (NT) {
-    typedef __attribute__((ext_vector_type(4))) float f4;
-    const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p) + i);
-    return make_float4(v.x, v.y, v.z, v.w);
-  } else {
-    return reinterpret_cast<const float4*>(p)[i];
-  }
-}
-template <bool NT>
-__device__ __forceinline__ void stf4(float* p, long i, float a, float b, float c, float d) {
-  if constexpr (NT) {
-    typedef __attribute__((ext_vector_type(4))) float f4;
-    __builtin_nontemporal_store(f4{a, b, c, d}, reinterpret_cast<f4*>(p) + i);
-  } else {
-    reinterpret_cast<float4*>(p)[i] = make_float4(a, b, c, d);
-  }
-}
-
-// U float4 items per thread per iteration (items i, i + stride, ...): every item's four loads
-// are issued before any is used — U x 64 B of each thread in flight
-template <bool NT, int U>
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v,
-                                                    __bf16* __restrict__ sh, long n4, float lr,
-                                                    float b1, float b2, float eps, float wd,
-                                                    float bc1, float bc2, float gs,
-                                                    const int* __restrict__ t_dev) {
-  if (t_dev != nullptr) {  // step count on the device: graph-replayable bias correction
-    const float t = (float)__hip_atomic_load(t_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    bc1 = 1.f - exp2f(t * log2f(b1));
-    bc2 = 1.f - exp2f(t * log2f(b2));
-  }
-  const float rbc2 = rsqrtf(bc2);
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += stride * U) {
-    float4 pv[U], gv[U], mv[U], vv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long i = i0 + u * stride;
-      if (u == 0 || i < n4) {
-        pv[u] = ldf4<NT>(p, i);
-        gv[u] = ldf4<NT>(g, i);
-        mv[u] = ldf4<NT>(m, i);
-        vv[u] = ldf4<NT>(v, i);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long i = i0 + u * stride;
-      if (u > 0 && i >= n4) break;
-      float pa[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w}, ga[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w};
-      float ma[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w}, va[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float gq = ga[q] * gs;
-        pa[q] *= 1.f - lr * wd;
-        ma[q] = b1 * ma[q] + (1.f - b1) * gq;
-        va[q] = b2 * va[q] + (1.f - b2) * gq * gq;
-        float denom = sqrtf(va[q]) * rbc2 + eps;
-        pa[q] -= (lr / bc1) * ma[q] / denom;
-      }
-      stf4<NT>(p, i, pa[0], pa[1], pa[2], pa[3]);
-      stf4<NT>(m, i, ma[0], ma[1], ma[2], ma[3]);
-      stf4<NT>(v, i, va[0], va[1], va[2], va[3]);
-      if (sh != nullptr)
-        reinterpret_cast<uint2*>(sh)[i] = make_uint2(pack2(pa[0], pa[1]), pack2(pa[2], pa[3]));
-    }
-  }
-}
-
-void adamw_step(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr,
-                float b1, float b2, float eps, float wd, float bc1, float bc2, float grad_scale,
-                hipStream_t st, const int* t_dev) {
-  long n4 = n / 4;
-  // 32768 blocks: 5.10 TB/s at BERT-base size vs 4.63 with the default 8192 cap (more waves in
-  // flight per SIMD; tools/r3/adamw_lab.hip, profiles/r3_bert_gemm_splitk_adamw.txt)
-  static const int cap = [] {
-    const char* e = getenv("MIPIPE_ADAMW_BLOCKS");
-    return e == nullptr ? 32768 : atoi(e);
-  }();
-  // MIPIPE_ADAMW_UNROLL: float4 items in flight per thread (1, 2 or 4); 2 measured +0.7 % on
-  // BERT-base over 1 (profiles/r6_adamw_unroll.txt)
-  static const int unroll = [] {
-    const char* e = getenv("MIPIPE_ADAMW_UNROLL");
-    const int u = e != nullptr ? atoi(e) : 2;
-    return u == 4 ? 4 : u == 1 ? 1 : 2;
-  }();
-  auto go = [&](auto nt_c, auto u_c) {
-    constexpr bool NT = decltype(nt_c)::value;
-    constexpr int U = decltype(u_c)::value;
-    hipLaunchKernelGGL((adamw_kernel<NT, U>), dim3(grid1d(n4, U, cap)), dim3(256), 0, st, p, g,
-                       m, v, (__bf16*)shadow, n4, lr, b1, b2, eps, wd, bc1, bc2, grad_scale, t_dev);
-  };
-  const bool nt = (g_nt_store & 1024) != 0;
-  if (unroll == 4) {
-    if (nt) go(std::true_type(), std::integral_constant<int, 4>());
-    else go(std::false_type(), std::integral_constant<int, 4>());
-  } else if (unroll == 2) {
-    if (nt) go(std::true_type(), std::integral_constant<int, 2>());
-    else go(std::false_type(), std::integral_constant<int, 2>());
-  } else {
-    if (nt) go(std::true_type(), std::integral_constant<int, 1>());
-    else go(std::false_type(), std::integral_constant<int, 1>());
-  }
 }
 
 // ------------------------------------------------------------------------------ layout / data

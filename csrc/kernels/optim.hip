@@ -1,9 +1,13 @@
-// Layer-wise adaptive optimizers (LARS, LAMB) over the flat parameter buffer, with global-norm
-// gradient clipping and a learning rate that lives on the device.
+// The optimizers over the flat fp32 parameter buffer, one launch sequence for the whole model,
+// each also emitting the bf16 weight shadow: SGD-momentum and AdamW (one grid-stride launch), and
+// the layer-wise adaptive LARS and LAMB with global-norm gradient clipping and a learning rate
+// that lives on the device.  All of them reach memory through flat_access.hpp, which states the
+// access rules (streaming state, cached shadow, loads before uses, no load behind a branch).
 //
-// The flat buffer is cut into chunks of at most kOptimChunk elements, none crossing a segment
-// (parameter) boundary: chunk c = {segment, offset / 64, length, 0}, offset and length multiples
-// of 64.  Segment s = {weight decay (float bits), adapt flag, first chunk, chunk count}.  A step:
+// LARS / LAMB: the flat buffer is cut into chunks of at most kOptimChunk elements, none crossing
+// a segment (parameter) boundary: chunk c = {segment, offset / 64, length, 0}, offset and length
+// multiples of 64.  Segment s = {weight decay (float bits), adapt flag, first chunk, chunk
+// count}.  A step:
 //
 //   seg_sumsq / lamb_moments   one block per chunk: the chunk's two partial sums of squares into
 //                              part[2][nchunks] (fixed lane tree, wave partials in index order)
@@ -16,41 +20,105 @@
 // clip, ratios) are device memory, so a step captured into a hipGraph replays correctly.
 // Padding (alignment tails, reserved pad rows) is zero in p, g, m, v and its update is exactly
 // zero under both rules, so it stays zero.
-#include "common.hpp"
-#include "launchers.hpp"
+#include "flat_access.hpp"
 
 namespace mipipe {
 
 namespace {
 
-constexpr int kItems = kOptimChunk / 4 / 256;  // float4 items per thread of a full chunk
-static_assert(kOptimChunk % 1024 == 0, "a chunk is a whole number of 256-thread float4 rounds");
-
-// streaming (non-temporal) access to the fp32 state, touched once per pass (g_nt_store & 1024)
-typedef __attribute__((ext_vector_type(4))) float f4v;
-template <bool NT>
-__device__ __forceinline__ float4 ld4(const float* p, long i) {
-  if constexpr (NT) {
-    const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p) + i);
-    return make_float4(v.x, v.y, v.z, v.w);
-  } else {
-    return reinterpret_cast<const float4*>(p)[i];
-  }
-}
-template <bool NT>
-__device__ __forceinline__ void st4(float* p, long i, const float* a) {
-  if constexpr (NT) {
-    __builtin_nontemporal_store(f4v{a[0], a[1], a[2], a[3]}, reinterpret_cast<f4v*>(p) + i);
-  } else {
-    reinterpret_cast<float4*>(p)[i] = make_float4(a[0], a[1], a[2], a[3]);
-  }
+int grid1d(long work, int per_thread = 1, int cap = 8192) {
+  long g = (work / per_thread + 255) / 256;
+  return (int)std::max<long>(1, std::min<long>(g, cap));
 }
 
-// A chunk entry the kernels may act on: inside the buffer, 64-aligned, of a known segment.  The
-// host builds the table from FlatParamSpace.ranges(); a block given anything else does nothing.
-__device__ __forceinline__ bool chunk_ok(const int4& c, long n, int nseg) {
-  return c.x >= 0 && c.x < nseg && c.y >= 0 && c.z > 0 && c.z <= kOptimChunk && (c.z & 63) == 0 &&
-         (long)c.y * 64 + c.z <= n;
+// SGD ([torch] optim/sgd.py:354-380): g += wd*p; m = momentum*m + (1-damp)*g (m = g first);
+// p -= lr * (nesterov ? g + momentum*m : m).  n % 4 == 0.  Cached accesses, a plain grid-stride
+// loop; the momentum load stays behind mom != 0 because m aliases the gradient buffer when the
+// momentum is 0.
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                  float* __restrict__ m, __bf16* __restrict__ sh,
+                                                  long n4, float lr, float mom, float damp, float wd,
+                                                  bool nesterov, bool first, float gs) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
+       i += (long)gridDim.x * blockDim.x) {
+    float4 pv = ld4<false>(p, i);
+    float4 gv = ld4<false>(g, i);
+    float pa[4] = {pv.x, pv.y, pv.z, pv.w};
+    float ga[4] = {gv.x * gs, gv.y * gs, gv.z * gs, gv.w * gs};
+    if (mom != 0.f) {
+      float ma[4];
+      unpack(ld4<false>(m, i), ma);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float d = ga[q] + wd * pa[q];
+        ma[q] = first ? d : mom * ma[q] + (1.f - damp) * d;
+        float upd = nesterov ? d + mom * ma[q] : ma[q];
+        pa[q] -= lr * upd;
+      }
+      st4<false>(m, i, ma);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) pa[q] -= lr * (ga[q] + wd * pa[q]);
+    }
+    st4<false>(p, i, pa);
+    st_shadow(sh, i, pa);
+  }
+}
+
+// AdamW, grid-stride with U float4 items per thread per iteration (items i0, i0 + stride, ...):
+// every item's four loads are issued before any is used.  The first item is in range by the loop
+// condition; the later ones are guarded (the items are a grid stride apart, so there is no
+// neighbour to clamp to).
+template <bool NT, int U>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v,
+                                                    __bf16* __restrict__ sh, long n4, float lr,
+                                                    float b1, float b2, float eps, float wd,
+                                                    float bc1, float bc2, float gs,
+                                                    const int* __restrict__ t_dev) {
+  if (t_dev != nullptr) {  // step count on the device: graph-replayable bias correction
+    const float t = (float)__hip_atomic_load(t_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bc1 = 1.f - exp2f(t * log2f(b1));
+    bc2 = 1.f - exp2f(t * log2f(b2));
+  }
+  const float rbc2 = rsqrtf(bc2);
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += stride * U) {
+    float4 pv[U], gv[U], mv[U], vv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = i0 + u * stride;
+      if (u == 0 || i < n4) {
+        pv[u] = ld4<NT>(p, i);
+        gv[u] = ld4<NT>(g, i);
+        mv[u] = ld4<NT>(m, i);
+        vv[u] = ld4<NT>(v, i);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = i0 + u * stride;
+      if (u > 0 && i >= n4) break;
+      float pa[4], ga[4], ma[4], va[4];
+      unpack(pv[u], pa);
+      unpack(gv[u], ga);
+      unpack(mv[u], ma);
+      unpack(vv[u], va);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float gq = ga[q] * gs;
+        pa[q] *= 1.f - lr * wd;
+        ma[q] = b1 * ma[q] + (1.f - b1) * gq;
+        va[q] = b2 * va[q] + (1.f - b2) * gq * gq;
+        float denom = sqrtf(va[q]) * rbc2 + eps;
+        pa[q] -= (lr / bc1) * ma[q] / denom;
+      }
+      st4<NT>(p, i, pa);
+      st4<NT>(m, i, ma);
+      st4<NT>(v, i, va);
+      st_shadow(sh, i, pa);
+    }
+  }
 }
 
 // Block sums of two per-thread values (256 threads): xor butterfly inside each wave (every lane
@@ -68,6 +136,11 @@ __device__ __forceinline__ void block_sum2_store(float a, float b, float* out_a,
     *out_a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
     *out_b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
   }
+}
+
+// x0^2 + x1^2 + x2^2 + x3^2 with the roundings spelled out
+__device__ __forceinline__ float sumsq(const float (&x)[4]) {
+  return __fmaf_rn(x[3], x[3], __fmaf_rn(x[2], x[2], __fmaf_rn(x[0], x[0], x[1] * x[1])));
 }
 
 __device__ __forceinline__ float sumsq4(const float4& v, float s) {
@@ -99,10 +172,11 @@ __device__ __forceinline__ float lamb_u(float w, float m, float v, const LambSte
   return __fmaf_rn(wd, w, __fdiv_rn(__fmul_rn(m, s.rbc1), den));
 }
 
-// part[0][c] = sum w^2 (WITH_W, else 0), part[1][c] = sum (g gs)^2 over chunk c.  U items of each
-// array are loaded before any is used.  No load sits behind a branch (the compiler would close it
-// with a full vmcnt(0) drain): a lane past the chunk's end re-reads the chunk's last item and adds
-// zero — the same in the kernels below, whose stores alone are conditional.
+// part[0][c] = sum w^2 (WITH_W, else 0 and p is not read), part[1][c] = sum (g gs)^2 over chunk
+// c.  The chunk walk written out, without a branch: a lane past the chunk's end re-reads the
+// chunk's last item and adds zero.  It stays written out because its sums are left to the
+// compiler's contraction, which follows the shape of this loop: restated on chunk_walk it no
+// longer gave the bits it gives here.
 template <bool NT, bool WITH_W, int U>
 __global__ __launch_bounds__(256) void seg_sumsq_kernel(const float* __restrict__ p,
                                                         const float* __restrict__ g,
@@ -114,7 +188,7 @@ __global__ __launch_bounds__(256) void seg_sumsq_kernel(const float* __restrict_
   const long base = (long)c.y * 16;
   const int len4 = c.z >> 2;
   float aw = 0.f, ag = 0.f;
-  for (int r = 0; r < kItems && r * 256 < len4; r += U) {
+  for (int r = 0; r < kChunkRounds && r * 256 < len4; r += U) {
     float4 pv[U], gv[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -134,7 +208,8 @@ __global__ __launch_bounds__(256) void seg_sumsq_kernel(const float* __restrict_
 
 // LAMB moments: m = b1 m + (1 - b1) g', v = b2 v + (1 - b2) g'^2 in place (g' = g gs clip), and
 // part[0][c] = sum w^2, part[1][c] = sum u^2 over chunk c.  scal[1] is the clip coefficient
-// (scal null: no clipping).
+// (scal null: no clipping).  Each sum of two products is written as the fma it is computed as
+// (the first product fused), so the bits do not hang on the compiler's choice of contraction.
 template <bool NT, int U>
 __global__ __launch_bounds__(256) void lamb_moments_kernel(
     const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -147,43 +222,26 @@ __global__ __launch_bounds__(256) void lamb_moments_kernel(
   const float wd = __int_as_float(segs[c.x].x);
   const float gsc = scal != nullptr ? gs * scal[1] : gs;  // no scal: no clipping
   const LambStep ls = lamb_step_scalars(t_dev, lnb1, lnb2);
-  const long base = (long)c.y * 16;
-  const int len4 = c.z >> 2;
   float aw = 0.f, au = 0.f;
-  for (int r = 0; r < kItems && r * 256 < len4; r += U) {
-    float4 pv[U], gv[U], mv[U], vv[U];
+  chunk_walk<NT, U, 4>(c, {p, g, m, v}, [&](long i, const float4(&x)[4]) {
+    float pa[4], ga[4], ma[4], va[4];
+    unpack(x[0], pa);
+    unpack(x[1], ga);
+    unpack(x[2], ma);
+    unpack(x[3], va);
+    float ua[4];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long j = base + min((r + u) * 256 + (int)threadIdx.x, len4 - 1);
-      pv[u] = ld4<NT>(p, j);
-      gv[u] = ld4<NT>(g, j);
-      mv[u] = ld4<NT>(m, j);
-      vv[u] = ld4<NT>(v, j);
+    for (int q = 0; q < 4; ++q) {
+      const float gq = ga[q] * gsc;
+      ma[q] = __fmaf_rn(b1, ma[q], omb1 * gq);
+      va[q] = __fmaf_rn(b2, va[q], omb2 * gq * gq);
+      ua[q] = lamb_u(pa[q], ma[q], va[q], ls, eps, wd);
     }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = (r + u) * 256 + threadIdx.x;
-      if (i >= len4) break;
-      const float pa[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w};
-      const float ga[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w};
-      float ma[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w};
-      float va[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
-      float sw = 0.f, su = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float gq = ga[q] * gsc;
-        ma[q] = b1 * ma[q] + omb1 * gq;
-        va[q] = b2 * va[q] + omb2 * gq * gq;
-        const float uq = lamb_u(pa[q], ma[q], va[q], ls, eps, wd);
-        sw += pa[q] * pa[q];
-        su += uq * uq;
-      }
-      aw += sw;
-      au += su;
-      st4<NT>(m, base + i, ma);
-      st4<NT>(v, base + i, va);
-    }
-  }
+    aw += sumsq(pa);
+    au += sumsq(ua);
+    st4<NT>(m, i, ma);
+    st4<NT>(v, i, va);
+  });
   block_sum2_store(aw, au, part + blockIdx.x, part + nchunks + blockIdx.x);
 }
 
@@ -275,7 +333,7 @@ __global__ __launch_bounds__(1024) void seg_finish_kernel(
 }
 
 // LARS: d = r (g' + wd w), m = mu m + d, w -= lr m; g' = g gs clip.  Writes p, m and the bf16
-// shadow (cached: the next forward reads it).
+// shadow.  The fmas are spelled out as in lamb_moments_kernel.
 template <bool NT, int U>
 __global__ __launch_bounds__(256) void lars_apply_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -288,37 +346,21 @@ __global__ __launch_bounds__(256) void lars_apply_kernel(
   const float r = ratio[c.x];
   const float lr = scal[0];
   const float gsc = gs * scal[1];
-  const long base = (long)c.y * 16;
-  const int len4 = c.z >> 2;
-  for (int r0 = 0; r0 < kItems && r0 * 256 < len4; r0 += U) {
-    float4 pv[U], gv[U], mv[U];
+  chunk_walk<NT, U, 3>(c, {p, g, m}, [&](long i, const float4(&x)[3]) {
+    float pa[4], ga[4], ma[4];
+    unpack(x[0], pa);
+    unpack(x[1], ga);
+    unpack(x[2], ma);
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long j = base + min((r0 + u) * 256 + (int)threadIdx.x, len4 - 1);
-      pv[u] = ld4<NT>(p, j);
-      gv[u] = ld4<NT>(g, j);
-      mv[u] = ld4<NT>(m, j);
+    for (int q = 0; q < 4; ++q) {
+      const float d = r * __fmaf_rn(ga[q], gsc, wd * pa[q]);
+      ma[q] = __fmaf_rn(mu, ma[q], d);
+      pa[q] = __fmaf_rn(-lr, ma[q], pa[q]);
     }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = (r0 + u) * 256 + threadIdx.x;
-      if (i >= len4) break;
-      float pa[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w};
-      const float ga[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w};
-      float ma[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float d = r * (ga[q] * gsc + wd * pa[q]);
-        ma[q] = mu * ma[q] + d;
-        pa[q] -= lr * ma[q];
-      }
-      st4<NT>(p, base + i, pa);
-      st4<NT>(m, base + i, ma);
-      if (sh != nullptr)
-        reinterpret_cast<uint2*>(sh)[base + i] =
-            make_uint2(pack2(pa[0], pa[1]), pack2(pa[2], pa[3]));
-    }
-  }
+    st4<NT>(p, i, pa);
+    st4<NT>(m, i, ma);
+    st_shadow(sh, i, pa);
+  });
 }
 
 // LAMB: w -= lr r u with u recomputed from (w, m, v) by lamb_u — the moments pass stored m and
@@ -334,54 +376,67 @@ __global__ __launch_bounds__(256) void lamb_apply_kernel(
   const float wd = __int_as_float(segs[c.x].x);
   const float lrr = scal[0] * ratio[c.x];
   const LambStep ls = lamb_step_scalars(t_dev, lnb1, lnb2);
-  const long base = (long)c.y * 16;
-  const int len4 = c.z >> 2;
-  for (int r0 = 0; r0 < kItems && r0 * 256 < len4; r0 += U) {
-    float4 pv[U], mv[U], vv[U];
+  chunk_walk<NT, U, 3>(c, {p, m, v}, [&](long i, const float4(&x)[3]) {
+    float pa[4], ma[4], va[4];
+    unpack(x[0], pa);
+    unpack(x[1], ma);
+    unpack(x[2], va);
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long j = base + min((r0 + u) * 256 + (int)threadIdx.x, len4 - 1);
-      pv[u] = ld4<NT>(p, j);
-      mv[u] = ld4<NT>(m, j);
-      vv[u] = ld4<NT>(v, j);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = (r0 + u) * 256 + threadIdx.x;
-      if (i >= len4) break;
-      float pa[4] = {pv[u].x, pv[u].y, pv[u].z, pv[u].w};
-      const float ma[4] = {mv[u].x, mv[u].y, mv[u].z, mv[u].w};
-      const float va[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) pa[q] -= lrr * lamb_u(pa[q], ma[q], va[q], ls, eps, wd);
-      st4<NT>(p, base + i, pa);
-      if (sh != nullptr)
-        reinterpret_cast<uint2*>(sh)[base + i] =
-            make_uint2(pack2(pa[0], pa[1]), pack2(pa[2], pa[3]));
-    }
-  }
+    for (int q = 0; q < 4; ++q) pa[q] -= lrr * lamb_u(pa[q], ma[q], va[q], ls, eps, wd);
+    st4<NT>(p, i, pa);
+    st_shadow(sh, i, pa);
+  });
 }
 
-inline bool nt_state() { return (g_nt_store & 1024) != 0; }
-
 }  // namespace
+
+void sgd_step(float* p, const float* g, float* m, void* shadow, long n, float lr, float momentum,
+              float dampening, float wd, bool nesterov, bool first, float grad_scale,
+              hipStream_t st) {
+  long n4 = n / 4;
+  hipLaunchKernelGGL(sgd_kernel, dim3(grid1d(n4, 4)), dim3(256), 0, st, p, g, m, (__bf16*)shadow,
+                     n4, lr, momentum, dampening, wd, nesterov, first, grad_scale);
+}
+
+void adamw_step(float* p, const float* g, float* m, float* v, void* shadow, long n, float lr,
+                float b1, float b2, float eps, float wd, float bc1, float bc2, float grad_scale,
+                hipStream_t st, const int* t_dev) {
+  long n4 = n / 4;
+  // 32768 blocks: 5.10 TB/s at BERT-base size vs 4.63 with the default 8192 cap (more waves in
+  // flight per SIMD; tools/r3/adamw_lab.hip, profiles/r3_bert_gemm_splitk_adamw.txt)
+  static const int cap = [] {
+    const char* e = getenv("MIPIPE_ADAMW_BLOCKS");
+    return e == nullptr ? 32768 : atoi(e);
+  }();
+  // MIPIPE_ADAMW_UNROLL: float4 items in flight per thread (1, 2 or 4); 2 measured +0.7 % on
+  // BERT-base over 1 (profiles/r6_adamw_unroll.txt)
+  static const int unroll = [] {
+    const char* e = getenv("MIPIPE_ADAMW_UNROLL");
+    const int u = e != nullptr ? atoi(e) : 2;
+    return u == 4 ? 4 : u == 1 ? 1 : 2;
+  }();
+  dispatch_int<1, 2, 4>(unroll, [&](auto u_c) {
+    dispatch_nt([&](auto nt_c) {
+      constexpr bool NT = decltype(nt_c)::value;
+      constexpr int U = decltype(u_c)::value;
+      hipLaunchKernelGGL((adamw_kernel<NT, U>), dim3(grid1d(n4, U, cap)), dim3(256), 0, st, p, g,
+                         m, v, (__bf16*)shadow, n4, lr, b1, b2, eps, wd, bc1, bc2, grad_scale,
+                         t_dev);
+    });
+  });
+}
 
 void optim_seg_sumsq(const float* p, const float* g, const int* chunks, int nchunks, int nseg,
                      long n, float grad_scale, bool with_w, float* part, hipStream_t st) {
   if (nchunks <= 0) return;
-  auto go = [&](auto nt_c, auto w_c) {
-    constexpr bool NT = decltype(nt_c)::value;
-    constexpr bool W = decltype(w_c)::value;
-    hipLaunchKernelGGL((seg_sumsq_kernel<NT, W, 4>), dim3(nchunks), dim3(256), 0, st, p, g,
-                       (const int4*)chunks, nchunks, nseg, n, grad_scale, part);
-  };
-  if (nt_state()) {
-    if (with_w) go(std::true_type(), std::true_type());
-    else go(std::true_type(), std::false_type());
-  } else {
-    if (with_w) go(std::false_type(), std::true_type());
-    else go(std::false_type(), std::false_type());
-  }
+  dispatch_nt([&](auto nt_c) {
+    dispatch_bool(with_w, [&](auto w_c) {
+      constexpr bool NT = decltype(nt_c)::value;
+      constexpr bool W = decltype(w_c)::value;
+      hipLaunchKernelGGL((seg_sumsq_kernel<NT, W, 4>), dim3(nchunks), dim3(256), 0, st, p, g,
+                         (const int4*)chunks, nchunks, nseg, n, grad_scale, part);
+    });
+  });
 }
 
 void optim_lamb_moments(const float* p, const float* g, float* m, float* v, const int* chunks,
@@ -390,14 +445,12 @@ void optim_lamb_moments(const float* p, const float* g, float* m, float* v, cons
                         float eps, const float* scal, const int* t_dev, float* part,
                         hipStream_t st) {
   if (nchunks <= 0) return;
-  auto go = [&](auto nt_c) {
+  dispatch_nt([&](auto nt_c) {
     constexpr bool NT = decltype(nt_c)::value;
     hipLaunchKernelGGL((lamb_moments_kernel<NT, 2>), dim3(nchunks), dim3(256), 0, st, p, g, m, v,
                        (const int4*)chunks, (const int4*)segs, nchunks, nseg, n, grad_scale, b1,
                        omb1, b2, omb2, lnb1, lnb2, eps, scal, t_dev, part);
-  };
-  if (nt_state()) go(std::true_type());
-  else go(std::false_type());
+  });
 }
 
 void optim_seg_finish(const float* part, int nchunks, const int* segs, int nseg, float* segtot,
@@ -412,14 +465,12 @@ void optim_lars_apply(float* p, const float* g, float* m, void* shadow, const in
                       const int* segs, int nchunks, int nseg, long n, float grad_scale,
                       float momentum, const float* ratio, const float* scal, hipStream_t st) {
   if (nchunks <= 0) return;
-  auto go = [&](auto nt_c) {
+  dispatch_nt([&](auto nt_c) {
     constexpr bool NT = decltype(nt_c)::value;
     hipLaunchKernelGGL((lars_apply_kernel<NT, 2>), dim3(nchunks), dim3(256), 0, st, p, g, m,
                        (__bf16*)shadow, (const int4*)chunks, (const int4*)segs, nseg, n,
                        grad_scale, momentum, ratio, scal);
-  };
-  if (nt_state()) go(std::true_type());
-  else go(std::false_type());
+  });
 }
 
 void optim_lamb_apply(float* p, const float* m, const float* v, void* shadow, const int* chunks,
@@ -427,14 +478,12 @@ void optim_lamb_apply(float* p, const float* m, const float* v, void* shadow, co
                       float eps, const float* ratio, const float* scal, const int* t_dev,
                       hipStream_t st) {
   if (nchunks <= 0) return;
-  auto go = [&](auto nt_c) {
+  dispatch_nt([&](auto nt_c) {
     constexpr bool NT = decltype(nt_c)::value;
     hipLaunchKernelGGL((lamb_apply_kernel<NT, 2>), dim3(nchunks), dim3(256), 0, st, p, m, v,
                        (__bf16*)shadow, (const int4*)chunks, (const int4*)segs, nseg, n, lnb1,
                        lnb2, eps, ratio, scal, t_dev);
-  };
-  if (nt_state()) go(std::true_type());
-  else go(std::false_type());
+  });
 }
 
 }  // namespace mipipe

@@ -493,24 +493,50 @@ def test_cross_entropy_split_fwd_bwd(V, valid, dtype):
         assert torch.equal(x.grad, grad)
 
 
-def test_sgd_and_adamw():
-    n = 4096 * 3
-    p = torch.randn(n, device=dev)
-    g = torch.randn(n, device=dev)
-    m = torch.randn(n, device=dev)
-    sh = torch.empty(n, device=dev, dtype=torch.bfloat16)
-    p2, m2 = p.clone(), m.clone()
-    for first in (True, False):
-        native().sgd_step(p, g, m, sh, 0.1, 0.9, 0.0, 1e-4, False, first, 1.0)
-        _ref.sgd_step(p2, g, m2, None, 0.1, 0.9, 0.0, 1e-4, False, first)
-        assert rel_err(p, p2) < 1e-6 and rel_err(m, m2) < 1e-6
-    assert torch.equal(sh, p.to(torch.bfloat16))
-    ea, eq = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-    ea2, eq2, p3 = ea.clone(), eq.clone(), p.clone()
-    for step in (1, 2, 3):
-        native().adamw_step(p, g, ea, eq, sh, 1e-3, 0.9, 0.999, 1e-8, 0.01, step, 1.0)
-        _ref.adamw_step(p3, g, ea2, eq2, None, 1e-3, 0.9, 0.999, 1e-8, 0.01, step)
-    assert rel_err(p, p3) < 1e-5
+@pytest.mark.parametrize("stream", [True, False], ids=["stream", "cached"])
+@pytest.mark.parametrize("n", [4, 1028, 12288])
+def test_sgd_and_adamw(n, stream):
+    """n = 4: one float4 item; 1028: 257 items, so exactly one second-item slot of AdamW's unroll
+    of 2 is live and the rest are past the end; 12288: whole blocks.  With the fp32 state streamed
+    (bit 1024 of the nt-store mask) and cached.  Every buffer is the head of an allocation 64
+    elements longer, whose tail must stay as it was."""
+    C = native()
+    PAD, MARK = 64, 7.0
+
+    def padded(src, dtype=torch.float32):
+        full = torch.full((n + PAD,), MARK, device=dev, dtype=dtype)
+        full[:n] = src
+        return full, full[:n]
+
+    def tails_untouched(*fulls):
+        return all(bool((f[n:] == MARK).all()) for f in fulls)
+
+    saved = C.get_nt_store()
+    try:
+        C.set_nt_store(saved | 1024 if stream else saved & ~1024)
+        g = torch.randn(n, device=dev)
+        pf, p = padded(torch.randn(n, device=dev))
+        mf, m = padded(torch.randn(n, device=dev))
+        shf, sh = padded(torch.zeros(n, device=dev), torch.bfloat16)
+        with pytest.raises(RuntimeError, match="shadow mismatch"):  # a check, nothing is launched
+            C.sgd_step(p, g, m, sh.float(), 0.1, 0.9, 0.0, 1e-4, False, True, 1.0)
+        p2, m2 = p.clone(), m.clone()
+        for first in (True, False):
+            C.sgd_step(p, g, m, sh, 0.1, 0.9, 0.0, 1e-4, False, first, 1.0)
+            _ref.sgd_step(p2, g, m2, None, 0.1, 0.9, 0.0, 1e-4, False, first)
+            assert rel_err(p, p2) < 1e-6 and rel_err(m, m2) < 1e-6
+        assert torch.equal(sh, p.to(torch.bfloat16))
+        eaf, ea = padded(torch.zeros(n, device=dev))
+        eqf, eq = padded(torch.zeros(n, device=dev))
+        ea2, eq2, p3 = ea.clone(), eq.clone(), p.clone()
+        for step in (1, 2, 3):
+            C.adamw_step(p, g, ea, eq, sh, 1e-3, 0.9, 0.999, 1e-8, 0.01, step, 1.0)
+            _ref.adamw_step(p3, g, ea2, eq2, None, 1e-3, 0.9, 0.999, 1e-8, 0.01, step)
+        assert rel_err(p, p3) < 1e-5
+        assert torch.equal(sh, p.to(torch.bfloat16))
+        assert tails_untouched(pf, mf, shf, eaf, eqf)
+    finally:
+        C.set_nt_store(saved)
 
 
 def test_nchw_to_nhwc_and_synthetic():
