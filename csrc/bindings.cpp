@@ -13,6 +13,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "common/augment.hpp"
 #include "kernels/launchers.hpp"
 
 using torch::Tensor;
@@ -1866,6 +1867,57 @@ std::tuple<Tensor, Tensor> record_decode_rrc(Tensor rec, Tensor idx, Tensor affi
   return {x, y};
 }
 
+// TrivialAugmentWide of whole records on the device (augment.hip): rec [n, label_bytes + C*H*W]
+// uint8, idx [n] int64 -> a new record tensor of the same layout, for the decode kernels to read.
+// force < 0: the op is a hash of (seed, epoch, idx); else op | m << 8 | (sign is +) << 16.
+Tensor record_augment(Tensor rec, Tensor idx, int64_t C, int64_t H, int64_t W, uint64_t seed,
+                      int64_t epoch, int64_t label_bytes, int64_t force, int64_t parts) {
+  check_cuda(rec, "rec");
+  check_cuda(idx, "idx");
+  c10::DeviceGuard g(rec.device());
+  TORCH_CHECK(rec.scalar_type() == at::kByte, "rec must be uint8, got ", rec.scalar_type());
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64, got ", idx.scalar_type());
+  TORCH_CHECK(idx.device() == rec.device(), "rec and idx must be on one device");
+  TORCH_CHECK(C == 1 || C == 3, "record_augment needs 1 or 3 channels, got ", C);
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= 32768 && W <= 32768 && C * H * W < (1ll << 31) - 16,
+              "bad image shape (H, W in [1, 32768])");
+  TORCH_CHECK(label_bytes >= 1 && label_bytes <= 8, "label_bytes must be in [1, 8]");
+  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == label_bytes + C * H * W, "rec must be [n, ",
+              label_bytes + C * H * W, "] (label bytes + C*H*W)");
+  TORCH_CHECK(rec.is_contiguous() && idx.is_contiguous(), "rec and idx must be contiguous");
+  const int64_t n = rec.size(0);
+  TORCH_CHECK(idx.dim() == 1 && idx.size(0) == n, "idx must be [n]");
+  TORCH_CHECK(mipipe_aug::force_ok(force), "bad force word ", force,
+              " (op | m << 8 | sign << 16, op < 14, m < 31)");
+  TORCH_CHECK(parts >= 0 && parts <= 64, "parts must be in [0, 64] (0: chosen by size)");
+  auto out = torch::empty_like(rec);
+  if (n == 0) return out;
+  mipipe::record_augment(rec.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), out.data_ptr<uint8_t>(),
+                         n, (int)C, (int)H, (int)W, (int)label_bytes, seed, (uint64_t)epoch,
+                         (long)force, (int)parts, stream());
+  return out;
+}
+
+// Random Erasing in place on the decoded batch x [n, C, Ho, Wo] (fp32 / bf16): the box of sample
+// idx[s] (a hash of seed, epoch and idx[s]; applied with probability pq / 2^24) becomes 0.0.
+Tensor batch_erase_(Tensor x, Tensor idx, uint64_t seed, int64_t epoch, int64_t pq) {
+  check_act(x, "x");
+  check_cuda(idx, "idx");
+  c10::DeviceGuard g(x.device());
+  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64, got ", idx.scalar_type());
+  TORCH_CHECK(idx.device() == x.device(), "x and idx must be on one device");
+  TORCH_CHECK(x.dim() == 4, "x must be [n, C, Ho, Wo], got ", x.dim(), " dimensions");
+  const int64_t n = x.size(0), C = x.size(1), Ho = x.size(2), Wo = x.size(3);
+  TORCH_CHECK(Ho <= 32768 && Wo <= 32768 && C * Ho * Wo < (1ll << 31) - 4 * C * Ho,
+              "sample too large (Ho, Wo <= 32768, C*Ho*Wo < 2^31)");
+  TORCH_CHECK(idx.dim() == 1 && idx.size(0) == n && idx.is_contiguous(), "idx must be [n]");
+  TORCH_CHECK(pq >= 0 && pq <= (1 << 24), "pq must be in [0, 2^24], got ", pq);
+  if (x.numel() == 0 || pq == 0) return x;
+  mipipe::batch_erase(x.data_ptr(), is_f32(x), idx.data_ptr<int64_t>(), n, (int)C, (int)Ho,
+                      (int)Wo, seed, (uint64_t)epoch, (uint32_t)pq, stream());
+  return x;
+}
+
 // ------------------------------------------------------------------------------- transformer ops
 Tensor gelu_fwd(Tensor x) {
   check_bf16(x, "x");
@@ -2578,6 +2630,13 @@ PYBIND11_MODULE(_C, m) {
         py::arg("affine"), py::arg("C"), py::arg("H"), py::arg("W"), py::arg("Ho"), py::arg("Wo"),
         py::arg("seed"), py::arg("epoch"), py::arg("flip"), py::arg("train"),
         py::arg("label_bytes"), py::arg("dtype"));
+  m.def("record_augment", &record_augment, py::arg("rec"), py::arg("idx"), py::arg("C"),
+        py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("epoch"), py::arg("label_bytes"),
+        py::arg("force") = -1, py::arg("parts") = 0);
+  m.def("record_augment_parts", &mipipe::record_augment_parts, py::arg("C"), py::arg("H"),
+        py::arg("W"));
+  m.def("batch_erase_", &batch_erase_, py::arg("x"), py::arg("idx"), py::arg("seed"),
+        py::arg("epoch"), py::arg("pq"));
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
   m.def("gemm_gelu", &gemm_gelu, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(),

@@ -489,6 +489,20 @@ void record_decode_rrc(const uint8_t* rec, const int64_t* idx, const float* affi
                        bool bf16_out, int64_t* y, long n, int C, int H, int W, int Ho, int Wo,
                        int label_bytes, uint64_t seed, uint64_t epoch, bool flip, bool train,
                        hipStream_t st);
+// Per-sample augmentation (augment.hip; definitions in common/augment.hpp, integer-only).
+// record_augment: TrivialAugmentWide of whole records, rec -> out of the same layout (label bytes
+// copied, out must not overlap rec), C in {1, 3}; the op of sample s is a hash of (seed, epoch,
+// idx[s]) unless force >= 0 pins it (op | m << 8 | (sign is +) << 16).  parts: blocks per sample
+// (0: record_augment_parts).  The decode kernels above then read `out`.
+int record_augment_parts(int C, int H, int W);
+void record_augment(const uint8_t* rec, const int64_t* idx, uint8_t* out, long n, int C, int H,
+                    int W, int label_bytes, uint64_t seed, uint64_t epoch, long force, int parts,
+                    hipStream_t st);
+// batch_erase: Random Erasing in place on the decoded batch x [n][C][Ho][Wo] (fp32 or bf16): the
+// box of mipipe_aug::erase_box(seed, epoch, idx[s], pq) becomes 0.0 in every channel; pq =
+// round(p * 2^24); Ho, Wo <= 32768.  A sample that is not erased touches no memory.
+void batch_erase(void* x, bool f32, const int64_t* idx, long n, int C, int Ho, int Wo,
+                 uint64_t seed, uint64_t epoch, uint32_t pq, hipStream_t st);
 // Fused ResNet stem on the packed input (stem.hip): conv 7x7/2 (packed K = 224, 64 channels,
 // 112 output columns) -> BN -> ReLU -> max-pool 3x3/2/1.
 //   stem_fwd_stats : shifted Σ, Σ² of bf16(y) per channel (conv recomputed, y not stored) ->

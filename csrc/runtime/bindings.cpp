@@ -65,7 +65,9 @@ PYBIND11_MODULE(_runtime, m) {
       .def_readwrite("raw", &LoaderConfig::raw)
       .def_readwrite("transform", &LoaderConfig::transform)
       .def_readwrite("out_h", &LoaderConfig::out_h)
-      .def_readwrite("out_w", &LoaderConfig::out_w);
+      .def_readwrite("out_w", &LoaderConfig::out_w)
+      .def_readwrite("auto_augment", &LoaderConfig::auto_augment)
+      .def_readwrite("erase_pq", &LoaderConfig::erase_pq);
 
   // the "rrc" transform's geometry (csrc/common/rrc.hpp), for tests against the Python definition
   m.def("rrc_box",

@@ -13,8 +13,12 @@
 // indices go through the same ring, and the transform runs on the GPU (csrc/kernels/records.hip).
 // LoaderConfig::transform "rrc": RandomResizedCrop + flip + Normalize to out_h x out_w instead of
 // the same-size crop (fill_rrc; geometry in csrc/common/rrc.hpp, shared with the device kernel).
+// LoaderConfig::auto_augment / erase_pq (training, non-raw modes): TrivialAugmentWide on the stored
+// image before the transform and Random Erasing on its output, from csrc/common/augment.hpp — the
+// functions the device kernels (csrc/kernels/augment.hip) use, so both decode modes agree.
 #include "runtime.hpp"
 
+#include "../common/augment.hpp"
 #include "../common/rrc.hpp"
 
 #include <fcntl.h>
@@ -53,6 +57,15 @@ RecordLoader::RecordLoader(const LoaderConfig& cfg) : cfg_(cfg) {
   } else if ((cfg_.out_h && cfg_.out_h != cfg_.H) || (cfg_.out_w && cfg_.out_w != cfg_.W)) {
     throw std::invalid_argument("out_h / out_w need transform \"rrc\"");
   }
+  if (!cfg_.auto_augment.empty() && cfg_.auto_augment != "ta_wide")
+    throw std::invalid_argument("auto_augment must be \"\" or \"ta_wide\"");
+  augment_ = cfg_.train && !cfg_.auto_augment.empty();
+  if (augment_ && cfg_.C != 1 && cfg_.C != 3)
+    throw std::invalid_argument("auto_augment needs 1 or 3 channels");
+  if (cfg_.erase_pq > (1u << 24)) throw std::invalid_argument("erase_pq must be in [0, 2^24]");
+  if (!cfg_.train) cfg_.erase_pq = 0;
+  if (cfg_.erase_pq && std::max(rrc_ ? cfg_.out_h : cfg_.H, rrc_ ? cfg_.out_w : cfg_.W) > 32768)
+    throw std::invalid_argument("erase_pq needs output extents <= 32768");
   out_per_ = rrc_ ? (size_t)cfg_.C * cfg_.out_h * cfg_.out_w : (size_t)cfg_.C * cfg_.H * cfg_.W;
   rec_bytes_ = (size_t)cfg_.label_bytes + (size_t)cfg_.C * cfg_.H * cfg_.W;
   for (auto& f : cfg_.files) {
@@ -122,6 +135,81 @@ void RecordLoader::start_epoch(const std::vector<int64_t>& indices, int64_t epoc
   cv_work_.notify_all();
 }
 
+// TrivialAugmentWide of one stored image (csrc/common/augment.hpp) with plain loops; the kernel
+// record_augment writes the same bytes.
+const uint8_t* RecordLoader::augmented(const uint8_t* img, int64_t gi, int64_t epoch,
+                                       std::vector<uint8_t>& tmp) const {
+  namespace aug = mipipe_aug;
+  if (!augment_) return img;
+  const int C = cfg_.C, H = cfg_.H, W = cfg_.W;
+  const size_t plane = (size_t)H * W;
+  tmp.resize((size_t)C * plane);
+  uint8_t* out = tmp.data();
+  const aug::Params par =
+      aug::ta_wide_params(aug::sample_word(cfg_.seed, (uint64_t)epoch, (uint64_t)gi), -1);
+  const int kind = aug::op_kind(par.op, C);
+  if (kind == aug::kLut) {
+    uint8_t lut[3][256];
+    if (par.op == aug::kAutoContrast || par.op == aug::kEqualize) {
+      for (int c = 0; c < C; ++c) {
+        uint32_t hist[256] = {0};
+        for (size_t p = 0; p < plane; ++p) ++hist[img[c * plane + p]];
+        aug::hist_lut(par.op, hist, lut[c]);
+      }
+    } else {
+      int mean = 0;
+      if (par.op == aug::kContrast) {
+        uint64_t sum = 0;
+        for (size_t p = 0; p < plane; ++p)
+          sum += (uint64_t)(C == 3 ? aug::grey(img[p], img[plane + p], img[2 * plane + p])
+                                   : (int)img[p]);
+        mean = aug::contrast_mean(sum, plane);
+      }
+      for (int v = 0; v < 256; ++v) {
+        const uint8_t t = (uint8_t)aug::point_lut(par, mean, v);
+        for (int c = 0; c < C; ++c) lut[c][v] = t;
+      }
+    }
+    for (int c = 0; c < C; ++c)
+      for (size_t p = 0; p < plane; ++p) out[c * plane + p] = lut[c][img[c * plane + p]];
+  } else if (kind == aug::kColorBlend) {
+    const int fq = aug::factor_q16(par);
+    for (size_t p = 0; p < plane; ++p) {
+      const int g = aug::grey(img[p], img[plane + p], img[2 * plane + p]);
+      for (int c = 0; c < 3; ++c)
+        out[c * plane + p] = (uint8_t)aug::blend(g, img[c * plane + p], fq);
+    }
+  } else if (kind == aug::kStencil) {
+    const int fq = aug::factor_q16(par);
+    for (int c = 0; c < C; ++c)
+      for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x)
+          out[c * plane + (size_t)y * W + x] =
+              (uint8_t)aug::sharpen(img + c * plane, y, x, H, W, fq);
+  } else {
+    const aug::Affine a = aug::affine_of(par);
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        int ys = 0, xs = 0;
+        const bool in = aug::affine_src(a, y, x, H, W, &ys, &xs);
+        for (int c = 0; c < C; ++c)
+          out[c * plane + (size_t)y * W + x] = in ? img[c * plane + (size_t)ys * W + xs] : 0;
+      }
+  }
+  return out;
+}
+
+// Random Erasing on one sample of the output, [C][Ho][Wo] floats: the box becomes 0.0
+void RecordLoader::erase(float* xs, int64_t gi, int64_t epoch, int Ho, int Wo) const {
+  namespace aug = mipipe_aug;
+  if (!cfg_.erase_pq) return;
+  const aug::EraseBox b = aug::erase_box(
+      aug::sample_word(cfg_.seed, (uint64_t)epoch, (uint64_t)gi), cfg_.erase_pq, Ho, Wo);
+  for (int c = 0; c < cfg_.C; ++c)
+    for (int y = b.y0; y < b.y0 + b.h; ++y)
+      for (int x = b.x0; x < b.x0 + b.w; ++x) xs[((size_t)c * Ho + y) * Wo + x] = 0.f;
+}
+
 void RecordLoader::fill(int slot, int64_t b, const std::vector<int64_t>& idx, int64_t epoch) {
   const int C = cfg_.C, H = cfg_.H, W = cfg_.W, P = cfg_.pad;
   const int64_t i0 = b * cfg_.batch;
@@ -129,13 +217,14 @@ void RecordLoader::fill(int slot, int64_t b, const std::vector<int64_t>& idx, in
   float* xo = slot_x_[slot].data();
   int64_t* yo = slot_y_[slot].data();
   const size_t plane = (size_t)H * W;
+  std::vector<uint8_t> tmp;
   for (int s = 0; s < n; ++s) {
     const int64_t gi = idx[i0 + s];
     const uint8_t* r = record(gi);
     int64_t label = 0;
     for (int k = 0; k < cfg_.label_bytes; ++k) label |= (int64_t)r[k] << (8 * k);
     yo[s] = label;
-    const uint8_t* img = r + cfg_.label_bytes;
+    const uint8_t* img = augmented(r + cfg_.label_bytes, gi, epoch, tmp);
     int dy = 0, dx = 0;
     bool flip = false;
     if (cfg_.train) {
@@ -163,6 +252,7 @@ void RecordLoader::fill(int slot, int64_t b, const std::vector<int64_t>& idx, in
         }
       }
     }
+    erase(xs, gi, epoch, H, W);
   }
   slot_n_[slot] = n;
 }
@@ -182,13 +272,14 @@ void RecordLoader::fill_rrc(int slot, int64_t b, const std::vector<int64_t>& idx
   // the column taps of one sample, the flip folded in: source columns and their weights
   std::vector<int> cx0(Wo), cx1(Wo);
   std::vector<float> lx0(Wo), lx1(Wo);
+  std::vector<uint8_t> tmp;
   for (int s = 0; s < n; ++s) {
     const int64_t gi = idx[i0 + s];
     const uint8_t* r = record(gi);
     int64_t label = 0;
     for (int k = 0; k < cfg_.label_bytes; ++k) label |= (int64_t)r[k] << (8 * k);
     yo[s] = label;
-    const uint8_t* img = r + cfg_.label_bytes;
+    const uint8_t* img = augmented(r + cfg_.label_bytes, gi, epoch, tmp);
     const rrc::Box bx = rrc::rrc_box(cfg_.seed, (uint64_t)epoch, (uint64_t)gi, H, W, cfg_.train,
                                      cfg_.flip);
     for (int x = 0; x < Wo; ++x) {
@@ -217,6 +308,7 @@ void RecordLoader::fill_rrc(int slot, int64_t b, const std::vector<int64_t>& idx
         }
       }
     }
+    erase(xs, gi, epoch, Ho, Wo);
   }
   slot_n_[slot] = n;
 }

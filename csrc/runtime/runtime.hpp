@@ -104,6 +104,12 @@ struct LoaderConfig {
   // (0 = stored size); the geometry is csrc/common/rrc.hpp, pad is not used.
   std::string transform = "crop";
   int out_h = 0, out_w = 0;
+  // Per-sample augmentation of the non-raw modes (csrc/common/augment.hpp; raw mode leaves both to
+  // the device, csrc/kernels/augment.hip), training only.  auto_augment: "" or "ta_wide"
+  // (TrivialAugmentWide on the stored image, before the transform; C must be 1 or 3).  erase_pq:
+  // Random Erasing's probability as round(p * 2^24), the box zeroed in the transform's output.
+  std::string auto_augment;
+  uint32_t erase_pq = 0;
 };
 
 class RecordLoader {
@@ -127,8 +133,13 @@ class RecordLoader {
   void fill(int slot, int64_t b, const std::vector<int64_t>& idx, int64_t epoch);
   void fill_rrc(int slot, int64_t b, const std::vector<int64_t>& idx, int64_t epoch);
   void fill_raw(int slot, int64_t b, const std::vector<int64_t>& idx);
+  // the image a transform reads: the stored one, or its augmentation written to tmp
+  const uint8_t* augmented(const uint8_t* img, int64_t gi, int64_t epoch,
+                           std::vector<uint8_t>& tmp) const;
+  void erase(float* xs, int64_t gi, int64_t epoch, int Ho, int Wo) const;
   LoaderConfig cfg_;
   bool rrc_ = false;
+  bool augment_ = false;
   size_t rec_bytes_ = 0;
   size_t out_per_ = 0;  // floats of one decoded sample
   std::vector<std::pair<const uint8_t*, size_t>> maps_;

@@ -33,6 +33,9 @@ from mipipe.parallel.sampler import DistributedSampler
 
 __all__ = ["write_records", "read_records", "write_synthetic_dataset", "reference_transform",
            "reference_rrc_box", "reference_transform_rrc", "RATIO_Q16", "RecordDataLoader",
+           "reference_augment_params", "reference_augment_op", "reference_augment",
+           "reference_erase_box", "augment_force", "erase_pq", "AUG_OPS", "AUG_POLICIES",
+           "COS_Q16", "SIN_Q16", "ERASE_RATIO_Q16",
            "CIFAR10_MEAN", "CIFAR10_STD", "IMAGENET_MEAN", "IMAGENET_STD", "dataset_files"]
 
 # task.py:249-251
@@ -254,6 +257,191 @@ def reference_transform_rrc(img: np.ndarray, index: int, epoch: int, seed: int, 
     return (v * (1.0 / (255.0 * s)) + (-m / s)).astype(np.float32)
 
 
+# ------------------------------------------------------------------ per-sample augmentation
+# TrivialAugmentWide on the stored uint8 image and Random Erasing on the normalised output
+# (csrc/common/augment.hpp holds the native copy).  Integer arithmetic only: these functions are
+# the contract the host loader and the device kernels (csrc/kernels/augment.hip) match byte for byte.
+AUG_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness",
+           "Color", "Contrast", "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")
+AUG_BINS = 31
+AUG_POLICIES = ("ta_wide",)
+_AUG_SALT = 0x5441776964654F70
+_ERASE_SALT = 0x52616E6445726173
+# round(65536 * cos / sin(4.5 deg * m)): Rotate's 31 angles
+COS_Q16 = (65536, 65334, 64729, 63725, 62328, 60547, 58393, 55879, 53020, 49834, 46341, 42562,
+           38521, 34242, 29753, 25080, 20252, 15299, 10252, 5142, 0, -5142, -10252, -15299,
+           -20252, -25080, -29753, -34242, -38521, -42562, -46341)
+SIN_Q16 = (0, 5142, 10252, 15299, 20252, 25080, 29753, 34242, 38521, 42562, 46341, 49834, 53020,
+           55879, 58393, 60547, 62328, 63725, 64729, 65334, 65536, 65334, 64729, 63725, 62328,
+           60547, 58393, 55879, 53020, 49834, 46341)
+# round(65536 * 0.3 * 11 ** (t/63)): Random Erasing's aspect ratios h/w, log-uniform over [0.3, 3.3]
+ERASE_RATIO_Q16 = (
+    19661, 20424, 21216, 22039, 22894, 23782, 24705, 25663, 26659, 27693, 28767, 29884, 31043,
+    32247, 33498, 34798, 36148, 37550, 39007, 40520, 42092, 43725, 45422, 47184, 49014, 50916,
+    52891, 54943, 57075, 59289, 61589, 63978, 66460, 69039, 71717, 74499, 77390, 80392, 83511,
+    86751, 90116, 93612, 97244, 101017, 104936, 109007, 113236, 117629, 122192, 126933, 131857,
+    136972, 142286, 147806, 153541, 159497, 165685, 172113, 178790, 185726, 192932, 200417,
+    208192, 216269)
+
+
+def _sample_word(seed: int, epoch: int, index: int) -> int:
+    """h0: the crop / flip word of sample ``index`` in ``epoch``."""
+    return _splitmix64(seed ^ _splitmix64(((epoch * 0x100000001B3) & _MASK64) ^ (index & _MASK64)))
+
+
+def augment_force(op, m: int, sign: int) -> int:
+    """The ``force`` word that pins an op (name or number), a magnitude bin and a sign (+1 / -1)."""
+    op = AUG_OPS.index(op) if isinstance(op, str) else int(op)
+    if not (0 <= op < len(AUG_OPS) and 0 <= m < AUG_BINS and sign in (1, -1)):
+        raise ValueError(f"bad augmentation op {(op, m, sign)}")
+    return op | (m << 8) | ((1 if sign > 0 else 0) << 16)
+
+
+def erase_pq(p: float) -> int:
+    """Random Erasing's probability as the 24-bit threshold ``round(p * 2**24)``."""
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"random_erase must be a probability in [0, 1], got {p}")
+    return int(round(float(p) * (1 << 24)))
+
+
+def reference_augment_params(seed: int, epoch: int, index: int, force: int = -1
+                             ) -> Tuple[int, int, int]:
+    """(op, m, sign) of TrivialAugmentWide for a sample: one of the 14 :data:`AUG_OPS`, one of 31
+    magnitude bins and a sign, from ``a = splitmix64(h0 ^ 0x5441776964654f70)``.  ``force`` >= 0
+    pins them instead: ``op | m << 8 | (sign > 0) << 16``."""
+    if force >= 0:
+        op, m, s = force & 0xFF, (force >> 8) & 0xFF, (force >> 16) & 1
+        if force >> 17 or op >= len(AUG_OPS) or m >= AUG_BINS:
+            raise ValueError(f"bad force word {force:#x}")
+        return op, m, (1 if s else -1)
+    a = _splitmix64(_sample_word(seed, epoch, index) ^ _AUG_SALT)
+    op = ((a & 0xFFFFFFFF) * len(AUG_OPS)) >> 32
+    m = (((a >> 32) & 0xFFFFFF) * AUG_BINS) >> 24
+    return op, m, (1 if (a >> 60) & 1 else -1)
+
+
+def _aug_blend(d, v, fq: int) -> np.ndarray:
+    return np.clip((d * (65536 - fq) + v * fq + 32768) >> 16, 0, 255)
+
+
+def _aug_grey(v: np.ndarray) -> np.ndarray:
+    if v.shape[0] == 1:
+        return v[0]
+    return (19595 * v[0] + 38470 * v[1] + 7471 * v[2] + 32768) >> 16
+
+
+def reference_augment_op(img: np.ndarray, op: int, m: int, sign: int) -> np.ndarray:
+    """One op of the table on a uint8 [C, H, W] image (C 1 or 3) -> uint8 [C, H, W]; the
+    definitions: Q16 factors, floor (arithmetic) shifts on integers, fill 0."""
+    C, H, W = img.shape
+    if C not in (1, 3):
+        raise ValueError(f"augmentation needs 1 or 3 channels, got {C}")
+    name = AUG_OPS[op]
+    v = img.astype(np.int64)
+    q = (64881 * m) // 30
+    fq = 65536 + sign * q
+    if name == "Identity" or (name == "Color" and C == 1):
+        out = v
+    elif name == "Brightness":
+        out = _aug_blend(0, v, fq)
+    elif name == "Color":
+        out = _aug_blend(_aug_grey(v)[None], v, fq)
+    elif name == "Contrast":
+        n = H * W
+        mean = (2 * int(_aug_grey(v).sum()) + n) // (2 * n)
+        out = _aug_blend(mean, v, fq)
+    elif name == "Sharpness":
+        s = v.copy()
+        if H > 2 and W > 2:
+            acc = sum(v[:, 1 + dy:H - 1 + dy, 1 + dx:W - 1 + dx]
+                      for dy in (-1, 0, 1) for dx in (-1, 0, 1)) + 4 * v[:, 1:-1, 1:-1]
+            s[:, 1:-1, 1:-1] = (acc + 6) // 13
+        out = _aug_blend(s, v, fq)
+    elif name == "Posterize":
+        bits = 8 - (2 * m + 5) // 10
+        out = v & ((0xFF << (8 - bits)) & 0xFF)
+    elif name == "Solarize":
+        out = np.where(2 * v < 510 - 17 * m, v, 255 - v)
+    elif name == "AutoContrast":
+        out = v.copy()
+        for c in range(C):
+            lo, hi = int(v[c].min()), int(v[c].max())
+            if hi > lo:
+                out[c] = ((v[c] - lo) * 255) // (hi - lo)
+    elif name == "Equalize":
+        out = v.copy()
+        for c in range(C):
+            h = np.bincount(img[c].ravel(), minlength=256).astype(np.int64)
+            nz = np.nonzero(h)[0]
+            if len(nz) < 2:
+                continue
+            step = (int(h.sum()) - int(h[nz[-1]])) // 255
+            if step == 0:
+                continue
+            cum = np.concatenate([[0], np.cumsum(h)[:-1]])
+            out[c] = np.minimum(255, (step // 2 + cum) // step)[v[c]]
+    else:  # the geometric ops: inverse nearest-neighbour map in doubled centred coordinates
+        A = D = 65536
+        B = Cc = tx = ty = 0
+        if name == "ShearX":
+            B = -sign * q
+        elif name == "ShearY":
+            Cc = -sign * q
+        elif name == "TranslateX":
+            tx = -sign * ((32 * m) // 30)
+        elif name == "TranslateY":
+            ty = -sign * ((32 * m) // 30)
+        else:
+            A = D = COS_Q16[m]
+            B, Cc = sign * SIN_Q16[m], -sign * SIN_Q16[m]
+        u = (2 * np.arange(W, dtype=np.int64) + 1 - W)[None, :]
+        w = (2 * np.arange(H, dtype=np.int64) + 1 - H)[:, None]
+        su = ((A * u + B * w) >> 16) + 2 * tx
+        sv = ((Cc * u + D * w) >> 16) + 2 * ty
+        xs, ys = (su + W) >> 1, (sv + H) >> 1
+        ok = (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+        out = np.where(ok[None], v[:, np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)], 0)
+    return out.astype(np.uint8)
+
+
+def reference_augment(img: np.ndarray, index: int, epoch: int, seed: int, force: int = -1
+                      ) -> np.ndarray:
+    """TrivialAugmentWide of the stored uint8 [C, H, W] image of sample ``index``: the op of
+    :func:`reference_augment_params` applied by :func:`reference_augment_op`.  It runs before the
+    crop / ``"rrc"`` transform, which then reads its output instead of the stored image."""
+    return reference_augment_op(img, *reference_augment_params(seed, epoch, index, force))
+
+
+def _erase_attempt(seed: int, epoch: int, index: int, pq: int, Ho: int, Wo: int
+                   ) -> Tuple[int, int, int, int, int]:
+    """(y0, x0, h, w, k): the erase box and the attempt that was accepted; k = -1 (and an empty
+    box) when the sample is not erased, k = -2 when all ten attempts were rejected."""
+    e = _splitmix64(_sample_word(seed, epoch, index) ^ _ERASE_SALT)
+    if (e & 0xFFFFFF) >= pq:
+        return 0, 0, 0, 0, -1
+    for k in range(10):
+        g = _splitmix64((e + k + 1) & _MASK64)
+        sq = 1311 + (((21627 - 1311) * (g & 0xFFFFFF)) >> 24)  # scale in Q16 over [0.02, 0.33)
+        area = (Ho * Wo * sq) >> 16
+        r = ERASE_RATIO_Q16[(g >> 24) & 63]
+        h = math.isqrt((area * r) >> 16)
+        w = math.isqrt((area << 16) // r)
+        if 0 < h < Ho and 0 < w < Wo:
+            g2 = _splitmix64(g)
+            return (g2 & 0xFFFFFFFF) % (Ho - h + 1), (g2 >> 32) % (Wo - w + 1), h, w, k
+    return 0, 0, 0, 0, -2
+
+
+def reference_erase_box(seed: int, epoch: int, index: int, pq: int, Ho: int, Wo: int
+                        ) -> Optional[Tuple[int, int, int, int]]:
+    """(y0, x0, h, w) of the Random Erasing box on the Ho x Wo output of a sample, or None: the
+    sample is erased iff the low 24 bits of ``e = splitmix64(h0 ^ 0x52616e6445726173)`` are below
+    ``pq`` = round(p * 2**24); torchvision's ``get_params`` (scale 0.02-0.33, log-uniform ratio
+    0.3-3.3, ten attempts) in integers.  Every channel of the box becomes 0.0."""
+    y0, x0, h, w, k = _erase_attempt(seed, epoch, index, pq, Ho, Wo)
+    return (y0, x0, h, w) if k >= 0 else None
+
+
 class RecordDataLoader:
     """Iterates (x [B,C,H,W] float32, y [B] int64) batches of this rank's shard.
 
@@ -270,7 +458,17 @@ class RecordDataLoader:
     ``transform="crop"`` (default) is RandomCrop(``pad``) + flip + Normalize at the stored size.
     ``transform="rrc"`` is :func:`reference_transform_rrc`: RandomResizedCrop + flip + Normalize
     in training, a 7/8 centre crop in evaluation, resized to ``out_size`` = (Ho, Wo) (default: the
-    stored size); ``pad`` is not used.  Both work with either ``decode``."""
+    stored size); ``pad`` is not used.  Both work with either ``decode``.
+
+    ``auto_augment="ta_wide"``: TrivialAugmentWide, one of 14 ops per image at one of 31
+    magnitudes (:func:`reference_augment`).  ``random_erase=p``: Random Erasing with probability
+    ``p`` (:func:`reference_erase_box`; scale 0.02-0.33, ratio 0.3-3.3, value 0.0).  The order is
+    augment -> crop / rrc -> erase: the augmentation acts on the *stored* uint8 image, before the
+    crop (torchvision augments the cropped image), so that the decode transforms and their
+    bit-exact contracts stay as they are; the erase acts on the normalised output.  Both are
+    integer-only functions of (seed, epoch, sample index), identical for ``decode="host"`` and
+    ``decode="device"`` (csrc/kernels/augment.hip: ``record_augment`` before the decode kernel,
+    ``batch_erase_`` after it).  ``train=False`` ignores both and launches nothing new."""
 
     def __init__(self, files: Sequence[str], shape: Sequence[int], batch_size: int,
                  sampler: Optional[DistributedSampler] = None, train: bool = True,
@@ -278,7 +476,8 @@ class RecordDataLoader:
                  seed: int = 0, workers: int = 8, prefetch: int = 4, drop_last: bool = False,
                  device: Optional[torch.device] = None, decode: str = "host",
                  out_dtype: torch.dtype = torch.float32, label_bytes: int = 1,
-                 transform: str = "crop", out_size: Optional[Sequence[int]] = None):
+                 transform: str = "crop", out_size: Optional[Sequence[int]] = None,
+                 auto_augment: Optional[str] = None, random_erase: float = 0.0):
         from mipipe.runtime import runtime, runtime_available
         if decode not in ("host", "device"):
             raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
@@ -286,7 +485,18 @@ class RecordDataLoader:
             raise ValueError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
         if transform not in ("crop", "rrc"):
             raise ValueError(f"transform must be 'crop' or 'rrc', got {transform!r}")
+        if auto_augment in ("none", ""):
+            auto_augment = None
+        if auto_augment is not None and auto_augment not in AUG_POLICIES:
+            raise ValueError(f"auto_augment must be None or one of {AUG_POLICIES}, "
+                             f"got {auto_augment!r}")
+        pq = erase_pq(random_erase)
         self.shape = tuple(int(v) for v in shape)
+        if auto_augment is not None and self.shape[0] not in (1, 3):
+            raise ValueError(f"auto_augment needs 1 or 3 channels, got {self.shape[0]}")
+        # evaluation is never augmented and never erased
+        self.auto_augment = auto_augment if train else None
+        self.erase_pq = pq if train else 0
         self.transform = transform
         if transform == "crop":
             if out_size is not None and tuple(out_size) != self.shape[1:]:
@@ -323,6 +533,11 @@ class RecordDataLoader:
             if transform == "rrc":
                 cfg.transform = "rrc"
                 cfg.out_h, cfg.out_w = self.out_size
+            if decode == "host":  # raw mode gathers only: the device augments and erases
+                if self.auto_augment is not None:
+                    cfg.auto_augment = self.auto_augment
+                if self.erase_pq:
+                    cfg.erase_pq = self.erase_pq
             self._ld = runtime().RecordLoader(cfg)
             n = len(self._ld)
         else:
@@ -394,13 +609,23 @@ class RecordDataLoader:
 
     def _reference(self, i: int) -> np.ndarray:
         """Sample ``i`` through the NumPy definition of the configured transform."""
+        img = self._imgs[i]
+        if self.auto_augment is not None:
+            img = reference_augment(img, i, self.epoch, self.seed)
         if self.transform == "rrc":
-            return reference_transform_rrc(self._imgs[i], i, self.epoch, self.seed, self.train,
-                                           self.out_size, self.flip and self.train, self.mean,
-                                           self.std)
-        return reference_transform(self._imgs[i], i, self.epoch, self.seed, self.train,
-                                   self.pad if self.train else 0, self.flip and self.train,
-                                   self.mean, self.std)
+            x = reference_transform_rrc(img, i, self.epoch, self.seed, self.train,
+                                        self.out_size, self.flip and self.train, self.mean,
+                                        self.std)
+        else:
+            x = reference_transform(img, i, self.epoch, self.seed, self.train,
+                                    self.pad if self.train else 0, self.flip and self.train,
+                                    self.mean, self.std)
+        if self.erase_pq:
+            box = reference_erase_box(self.seed, self.epoch, i, self.erase_pq, *x.shape[1:])
+            if box is not None:
+                y0, x0, h, w = box
+                x[:, y0:y0 + h, x0:x0 + w] = 0.0
+        return x
 
     def _iter_device(self, idx) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         """decode="device": upload the uint8 records + sample indices, transform on the device."""
@@ -408,13 +633,19 @@ class RecordDataLoader:
         epoch = self.epoch
 
         def decode(rec, gi):
+            if self.auto_augment is not None:
+                rec = K.record_augment(rec, gi, self.shape, self.seed, epoch, self.label_bytes)
             if self.transform == "rrc":
-                return K.record_decode_rrc(rec, gi, self._affine, self.shape, self.out_size,
-                                           self.seed, epoch, self.flip and self.train, self.train,
-                                           self.label_bytes, self.out_dtype)
-            return K.record_decode(rec, gi, self._affine, self.shape, self.seed, epoch,
-                                   self.pad if self.train else 0, self.flip and self.train,
-                                   self.train, self.label_bytes, self.out_dtype)
+                out = K.record_decode_rrc(rec, gi, self._affine, self.shape, self.out_size,
+                                          self.seed, epoch, self.flip and self.train, self.train,
+                                          self.label_bytes, self.out_dtype)
+            else:
+                out = K.record_decode(rec, gi, self._affine, self.shape, self.seed, epoch,
+                                      self.pad if self.train else 0, self.flip and self.train,
+                                      self.train, self.label_bytes, self.out_dtype)
+            if self.erase_pq:
+                K.batch_erase_(out[0], gi, self.seed, epoch, self.erase_pq)
+            return out
 
         if not self.native:
             for b in range(len(self)):

@@ -747,6 +747,34 @@ def record_decode(rec: Tensor, idx: Tensor, affine: Tensor, shape, seed: int, ep
     return x.to(dtype), y
 
 
+def record_augment(rec: Tensor, idx: Tensor, shape, seed: int, epoch: int, label_bytes: int = 1,
+                   force: int = -1) -> Tensor:
+    """TrivialAugmentWide on whole records (csrc/kernels/augment.hip's record_augment contract):
+    every image through ``data.records.reference_augment``, the label bytes copied."""
+    import numpy as np
+    from mipipe.data.records import reference_augment
+    C, H, W = shape
+    src = rec.cpu().numpy()
+    out = src.copy()
+    for s, gi in enumerate(idx.tolist()):
+        img = src[s, label_bytes:].reshape(C, H, W)
+        out[s, label_bytes:] = reference_augment(img, gi, epoch, seed, force).reshape(-1)
+    return torch.from_numpy(out).to(rec.device)
+
+
+def batch_erase_(x: Tensor, idx: Tensor, seed: int, epoch: int, pq: int) -> Tensor:
+    """Random Erasing in place (csrc/kernels/augment.hip's batch_erase contract): the box of
+    ``data.records.reference_erase_box`` of every sample becomes 0.0 in every channel."""
+    from mipipe.data.records import reference_erase_box
+    Ho, Wo = x.shape[2:]
+    for s, gi in enumerate(idx.tolist()):
+        box = reference_erase_box(seed, epoch, gi, pq, Ho, Wo)
+        if box is not None:
+            y0, x0, h, w = box
+            x[s, :, y0:y0 + h, x0:x0 + w] = 0
+    return x
+
+
 def record_decode_rrc(rec: Tensor, idx: Tensor, affine: Tensor, shape, out_size, seed: int,
                       epoch: int, flip: bool, train: bool, label_bytes: int = 1,
                       dtype=torch.float32) -> Tuple[Tensor, Tensor]:

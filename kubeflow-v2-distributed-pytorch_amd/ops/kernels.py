@@ -23,6 +23,7 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "adamw_step", "ema_update", "ema_swap", "ema_buffers_update", "ema_buffers_swap",
            "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
            "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "record_decode", "record_decode_rrc",
+           "record_augment", "batch_erase_",
            "use_native",
            "gconv_fwd", "gconv_dgrad", "gconv_wgrad", "chan_stats", "affine_act",
            "bn_generic_bwd_reduce", "bn_generic_bwd_apply", "avgpool2d_fwd", "avgpool2d_bwd"]
@@ -683,6 +684,30 @@ def record_decode_rrc(rec, idx, affine, shape, out_size, seed: int, epoch: int, 
                                           dtype)
     return _ref.record_decode_rrc(rec, idx, affine, (C, H, W), (Ho, Wo), int(seed), int(epoch),
                                   bool(flip), bool(train), int(label_bytes), dtype)
+
+
+def record_augment(rec, idx, shape, seed: int, epoch: int, label_bytes: int = 1,
+                   force: int = -1, parts: int = 0):
+    """TrivialAugmentWide on whole uint8 records ``rec`` [n, label_bytes + C*H*W] (C 1 or 3) with
+    global sample indices ``idx`` -> a new record tensor of the same layout (labels copied), which
+    ``record_decode`` / ``record_decode_rrc`` then read: byte for byte
+    ``data.records.reference_augment`` of every image.  ``force`` >= 0 pins the op
+    (``data.records.augment_force``); ``parts`` (native): blocks per sample, 0 = by size."""
+    C, H, W = (int(v) for v in shape)
+    if use_native(rec):
+        return native().record_augment(rec, idx, C, H, W, int(seed), int(epoch), int(label_bytes),
+                                       int(force), int(parts))
+    return _ref.record_augment(rec, idx, (C, H, W), int(seed), int(epoch), int(label_bytes),
+                               int(force))
+
+
+def batch_erase_(x, idx, seed: int, epoch: int, pq: int):
+    """Random Erasing in place on the decoded batch ``x`` [n, C, Ho, Wo] (fp32 / bf16): the box
+    ``data.records.reference_erase_box`` gives sample ``idx[s]`` becomes 0.0 in every channel;
+    ``pq`` = round(p * 2**24).  Returns ``x``."""
+    if use_native(x):
+        return native().batch_erase_(x, idx, int(seed), int(epoch), int(pq))
+    return _ref.batch_erase_(x, idx, int(seed), int(epoch), int(pq))
 
 
 # ----------------------------------------------------------------------------- vision.hip

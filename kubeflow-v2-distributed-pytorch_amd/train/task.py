@@ -44,6 +44,15 @@ Regularisers (all off by default; :mod:`mipipe.data.mix`):
     captured step's third input).  Evaluation is never mixed.  The step log line and
     ``metrics.json`` carry ``mix_mode`` and ``mix_lambda``.
 
+Per-sample augmentation of record data (off by default; needs ``--data-dir``):
+  * ``--auto-augment ta_wide``: TrivialAugmentWide, one of 14 ops per image at one of 31
+    magnitudes; ``--random-erase P``: Random Erasing with probability ``P``.  The order is augment
+    -> crop / rrc -> erase: the augmentation acts on the stored image, before the crop
+    (torchvision augments after it), the erase on the normalised batch.  Both are functions of
+    ``(random_seed, epoch, sample index)``, the same bits with ``--device-decode`` 0 and 1 (the
+    ``record_augment`` and ``batch_erase`` kernels); evaluation is never augmented.  The start-up
+    line and ``metrics.json`` carry ``auto_augment`` and ``random_erase``.
+
 Weight averaging (off by default; :class:`mipipe.optim.ModelEMA`):
   * ``--model-ema-decay D`` (0 = off) with ``--model-ema-steps N`` (average every N-th step) and
     ``--model-ema-warmup {0,1}`` (timm's ``min(D, (1+u)/(10+u))`` warm-up).  ``D`` is used as
@@ -318,6 +327,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "rrc = RandomResizedCrop + flip (7/8 centre crop for evaluation) resized "
                         "to the model's input size. Default: crop, or rrc when the data "
                         "directory's manifest.json stores another size than the model takes")
+    p.add_argument("--auto-augment", choices=["none", "ta_wide"], default="none",
+                   help="with --data-dir: ta_wide = TrivialAugmentWide on every training image "
+                        "(one random op of 14 at a random magnitude), applied to the stored image "
+                        "before the crop; on the device with --device-decode 1")
+    p.add_argument("--random-erase", type=float, default=0.0, metavar="P",
+                   help="with --data-dir: Random Erasing of the normalised training batch with "
+                        "probability P (scale 0.02-0.33, ratio 0.3-3.3, value 0)")
     p.add_argument("--train-samples", type=int, default=None)
     p.add_argument("--test-samples", type=int, default=None)
     p.add_argument("--num_classes", type=int, default=None,
@@ -457,6 +473,12 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
     # cudnn.deterministic (task.py:25-26) / cudnn.benchmark (task.py:244) analogues
     configure_kernels(use_gpu, args.deterministic)
 
+    if not 0.0 <= args.random_erase <= 1.0:
+        raise SystemExit(f"--random-erase must be a probability in [0, 1], got {args.random_erase}")
+    augmenting = args.auto_augment != "none" or args.random_erase > 0
+    if augmenting and not args.data_dir:
+        raise SystemExit("--auto-augment / --random-erase act on record data: they need "
+                         "--data-dir (synthetic on-device data is not augmented)")
     if args.pretrained:
         print(f"=> using pre-trained model '{args.arch}'")  # task.py:167
     else:
@@ -571,10 +593,17 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         rkw = {"label_bytes": label_bytes}
         if record_transform == "rrc":
             rkw.update(transform="rrc", out_size=(H, W))
+        akw = {}
+        if augmenting:
+            akw = {"auto_augment": None if args.auto_augment == "none" else args.auto_augment,
+                   "random_erase": args.random_erase}
+            print(f"=> record augmentation: auto_augment={args.auto_augment} "
+                  f"random_erase={args.random_erase} (augment -> {record_transform} -> erase, "
+                  f"decode={decode})", flush=True)
         probe = REC.RecordDataLoader(train_files, stored, args.batch_size, train=True,
                                      pad=pad, mean=mean, std=std, seed=args.random_seed,
                                      workers=max(1, args.workers), device=device, decode=decode,
-                                     **rkw)
+                                     **rkw, **akw)
         train_sampler = DistributedSampler(probe.num_samples_total, seed=args.random_seed)
         probe.sampler = train_sampler
         train_loader = probe
@@ -756,6 +785,8 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         metrics["lr"] = float(optimizer.last_lr().item())
     if mixer is not None:
         metrics.update(mix_mode=mixer.last_mode, mix_lambda=mixer.last_lambda)
+    if augmenting:
+        metrics.update(auto_augment=args.auto_augment, random_erase=args.random_erase)
     if ema is not None:
         metrics.update(accuracy_ema=accuracy_ema, ema_updates=ema.num_updates())
     if eval_meter is not None:
