@@ -5,68 +5,15 @@
 // call raises a Python error instead of faulting the GPU.  Outputs are allocated with the torch
 // caching allocator and kernels run on the current HIP stream (graph-capturable).
 #include <torch/extension.h>
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <c10/core/DeviceGuard.h>
-#include <pybind11/stl.h>
 
-#include <string>
 #include <unordered_map>
-#include <vector>
 
-#include "common/augment.hpp"
-#include "kernels/launchers.hpp"
+#include "bind/common.hpp"
 
-using torch::Tensor;
-using c10::optional;
+// the shared helpers and checks (stream, check_*, ce_args, check_records ...): bind/common.hpp
+using namespace mipipe_bind;
 
 namespace {
-
-hipStream_t stream() { return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
-
-void check_cuda(const Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-}
-void check_bf16(const Tensor& t, const char* name) {
-  check_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bfloat16, got ", t.scalar_type());
-}
-// activation tensors: bf16 (mixed precision) or fp32 (the reference's precision)
-void check_act(const Tensor& t, const char* name) {
-  check_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat, name,
-              " must be bfloat16 or float32, got ", t.scalar_type());
-}
-void check_same(const Tensor& t, const Tensor& ref, const char* name) {
-  check_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == ref.scalar_type(), name, " must be ", ref.scalar_type(),
-              " like the other operands, got ", t.scalar_type());
-}
-bool is_f32(const Tensor& t) { return t.scalar_type() == at::kFloat; }
-void check_f32(const Tensor& t, const char* name) {
-  check_cuda(t, name);
-  TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32, got ", t.scalar_type());
-}
-void check_vec(const Tensor& t, int64_t C, const char* name) {
-  check_f32(t, name);
-  TORCH_CHECK(t.numel() == C, name, " must have ", C, " elements, got ", t.numel());
-}
-const void* ptr_or_null(const optional<Tensor>& t) { return t.has_value() ? t->data_ptr() : nullptr; }
-float* fptr(const optional<Tensor>& t, int64_t n) {
-  if (!t.has_value()) return nullptr;
-  check_vec(*t, n, "gradient accumulator");
-  return t->data_ptr<float>();
-}
-// an on/off environment switch (unset: dflt); callers keep the result in a static: read once
-bool env_flag(const char* name, bool dflt) {
-  const char* v = getenv(name);
-  return v == nullptr ? dflt : atoi(v) != 0;
-}
-// fp32 workspace of a split-K conv plan (n elements; n == 0: no split, undefined / null)
-Tensor split_ws(long n, const Tensor& like) {
-  return n > 0 ? torch::empty({n}, like.options().dtype(at::kFloat)) : Tensor();
-}
-float* wsp(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 
 // bf16 operands go through buffer descriptors with 32-bit byte offsets (gemm_core.hpp kOOB,
 // gk_rsrc clamps the range): a larger bf16 tensor would read zeros, so every conv entry point
@@ -842,14 +789,6 @@ std::tuple<Tensor, optional<Tensor>> bn_act_bwd_apply(
 }
 
 // ------------------------------------------------------------------------------- pooling
-// torch's pooling output size (ceil_mode: the last window must start inside input or left pad)
-int pool_out(int L, int k, int s, int p, bool ceil_mode) {
-  int num = L + 2 * p - k;
-  int o = (ceil_mode ? (num + s - 1) / s : num / s) + 1;
-  if (ceil_mode && (o - 1) * s >= L + p) --o;
-  return o;
-}
-
 std::tuple<Tensor, Tensor> maxpool_fwd(Tensor x, int k, int s, int p, bool ceil_mode) {
   check_act(x, "x");
   c10::DeviceGuard g(x.device());
@@ -1329,219 +1268,7 @@ void touch(std::vector<Tensor> ts) {
   }
 }
 
-// ------------------------------------------------------------------------------- loss / optim
-// Split cross-entropy (training step): forward -> (loss, work = [count | row losses | row lse]),
-// backward -> grad from the saved logits and the upstream gradient (a device scalar).
-std::tuple<Tensor, Tensor> cross_entropy_fwd(Tensor logits, Tensor labels, double smoothing,
-                                             int64_t ignore_index, int64_t valid_cols) {
-  check_act(logits, "logits");
-  check_cuda(labels, "labels");
-  c10::DeviceGuard g(logits.device());
-  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
-  TORCH_CHECK(logits.dim() == 2 && labels.numel() == logits.size(0) && logits.is_contiguous(),
-              "CE shape mismatch");
-  const int R = logits.size(0), V = logits.size(1);
-  auto loss = torch::empty({}, logits.options().dtype(at::kFloat));
-  auto work = torch::empty({4 + 2 * (int64_t)R}, logits.options().dtype(at::kInt));
-  mipipe::cross_entropy_fwd(logits.data_ptr(), labels.data_ptr<int64_t>(), loss.data_ptr<float>(),
-                            R, V, (float)smoothing, ignore_index, work.data_ptr<int>(), stream(),
-                            is_f32(logits), (int)std::min<int64_t>(valid_cols > 0 ? valid_cols : V, V));
-  return {loss, work};
-}
-
-Tensor cross_entropy_bwd(Tensor logits, Tensor labels, Tensor work, Tensor gout, double smoothing,
-                         int64_t ignore_index, int64_t valid_cols) {
-  check_act(logits, "logits");
-  c10::DeviceGuard g(logits.device());
-  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && labels.numel() == logits.size(0),
-              "CE shape mismatch");
-  const int R = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == 4 + 2 * (int64_t)R,
-              "CE work buffer mismatch");
-  check_cuda(labels, "labels");
-  check_cuda(work, "work");
-  check_f32(gout, "gout");
-  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
-  TORCH_CHECK(gout.numel() == 1 && gout.device() == logits.device() &&
-              labels.device() == logits.device() && work.device() == logits.device(),
-              "gout must be one value; every operand on the logits' device");
-  auto grad = torch::empty_like(logits);
-  mipipe::cross_entropy_bwd(logits.data_ptr(), labels.data_ptr<int64_t>(), work.data_ptr<int>(),
-                            gout.data_ptr<float>(), grad.data_ptr(), R, V, (float)smoothing,
-                            ignore_index, stream(), is_f32(logits),
-                            (int)std::min<int64_t>(valid_cols > 0 ? valid_cols : V, V));
-  return grad;
-}
-
-std::tuple<Tensor, Tensor> cross_entropy_fwd_bwd(Tensor logits, Tensor labels, double smoothing,
-                                                 int64_t ignore_index, int64_t valid_cols) {
-  check_act(logits, "logits");
-  check_cuda(labels, "labels");
-  c10::DeviceGuard g(logits.device());
-  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
-  TORCH_CHECK(logits.dim() == 2 && labels.numel() == logits.size(0), "CE shape mismatch");
-  int R = logits.size(0), V = logits.size(1);
-  auto loss = torch::empty({}, logits.options().dtype(at::kFloat));
-  auto grad = torch::empty_like(logits);
-  auto work = torch::empty({4 + R}, logits.options().dtype(at::kInt));  // count + row losses
-  mipipe::cross_entropy_fwd_bwd(logits.data_ptr(), labels.data_ptr<int64_t>(), loss.data_ptr<float>(),
-                                grad.data_ptr(), R, V, (float)smoothing, ignore_index,
-                                work.data_ptr<int>(), stream(), is_f32(logits),
-                                (int)std::min<int64_t>(valid_cols > 0 ? valid_cols : V, V));
-  return {loss, grad};
-}
-
-// the device-side mix descriptor (mipipe/data/mix.py): fp32, >= 8 elements, on `ref`'s device
-void check_mix(const Tensor& mix, const Tensor& ref) {
-  check_f32(mix, "mix");
-  TORCH_CHECK(mix.numel() >= 8, "mix must hold at least 8 elements, got ", mix.numel());
-  TORCH_CHECK(mix.device() == ref.device(), "mix must be on the device of the other operands");
-}
-
-// Pair-target split cross-entropy (Mixup / CutMix): row r is labelled labels[r] with weight
-// mix[0] and labels[R-1-r] with weight 1 - mix[0]; same work layout as cross_entropy_fwd.
-std::tuple<Tensor, Tensor> cross_entropy_mixed_fwd(Tensor logits, Tensor labels, Tensor mix,
-                                                   double smoothing, int64_t valid_cols) {
-  check_act(logits, "logits");
-  check_cuda(labels, "labels");
-  check_mix(mix, logits);
-  c10::DeviceGuard g(logits.device());
-  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
-  TORCH_CHECK(logits.dim() == 2 && labels.numel() == logits.size(0) && logits.is_contiguous(),
-              "CE shape mismatch");
-  TORCH_CHECK(labels.device() == logits.device(), "labels must be on the logits' device");
-  const int R = logits.size(0), V = logits.size(1);
-  auto loss = torch::empty({}, logits.options().dtype(at::kFloat));
-  auto work = torch::empty({4 + 2 * (int64_t)R}, logits.options().dtype(at::kInt));
-  if (R == 0 || V == 0) return {loss.zero_(), work};
-  mipipe::cross_entropy_mixed_fwd(
-      logits.data_ptr(), labels.data_ptr<int64_t>(), mix.data_ptr<float>(),
-      loss.data_ptr<float>(), R, V, (float)smoothing, work.data_ptr<int>(), stream(),
-      is_f32(logits), (int)std::min<int64_t>(valid_cols > 0 ? valid_cols : V, V));
-  return {loss, work};
-}
-
-Tensor cross_entropy_mixed_bwd(Tensor logits, Tensor labels, Tensor mix, Tensor work, Tensor gout,
-                               double smoothing, int64_t valid_cols) {
-  check_act(logits, "logits");
-  check_mix(mix, logits);
-  c10::DeviceGuard g(logits.device());
-  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous() && labels.numel() == logits.size(0),
-              "CE shape mismatch");
-  const int R = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(work.scalar_type() == at::kInt && work.numel() == 4 + 2 * (int64_t)R,
-              "CE work buffer mismatch");
-  check_cuda(labels, "labels");
-  check_cuda(work, "work");
-  check_f32(gout, "gout");
-  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
-  TORCH_CHECK(gout.numel() == 1 && gout.device() == logits.device() &&
-              labels.device() == logits.device() && work.device() == logits.device(),
-              "gout must be one value; every operand on the logits' device");
-  auto grad = torch::empty_like(logits);
-  if (R == 0 || V == 0) return grad;
-  mipipe::cross_entropy_mixed_bwd(
-      logits.data_ptr(), labels.data_ptr<int64_t>(), mix.data_ptr<float>(), work.data_ptr<int>(),
-      gout.data_ptr<float>(), grad.data_ptr(), R, V, (float)smoothing, stream(), is_f32(logits),
-      (int)std::min<int64_t>(valid_cols > 0 ? valid_cols : V, V));
-  return grad;
-}
-
-// Mixup / CutMix of x [B, C, H, W] with its reverse, as the device descriptor says (mix.hip).
-// out: x itself (in place), another tensor of x's shape and type, or none (a new tensor).
-Tensor batch_mix(Tensor x, Tensor mix, optional<Tensor> out) {
-  check_act(x, "x");
-  check_mix(mix, x);
-  c10::DeviceGuard g(x.device());
-  TORCH_CHECK(x.dim() == 4, "x must be [B, C, H, W], got ", x.dim(), " dimensions");
-  const int64_t B = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  TORCH_CHECK(B < (1ll << 31) && C * H * W < (1ll << 31), "sample too large: C*H*W must be < 2^31");
-  Tensor o = out.has_value() ? *out : torch::empty_like(x);
-  if (out.has_value()) {
-    check_same(o, x, "out");
-    TORCH_CHECK(o.sizes() == x.sizes() && o.device() == x.device(),
-                "out must have x's shape and device");
-    const char* xb = static_cast<const char*>(x.data_ptr());
-    const char* ob = static_cast<const char*>(o.data_ptr());
-    const int64_t nb = (int64_t)x.numel() * x.element_size();
-    TORCH_CHECK(ob == xb || ob + nb <= xb || xb + nb <= ob, "out overlaps x without being x");
-  }
-  {
-    const char* mb = static_cast<const char*>(mix.data_ptr());
-    const char* ob = static_cast<const char*>(o.data_ptr());
-    const int64_t nb = (int64_t)o.numel() * o.element_size();
-    TORCH_CHECK(mb + mix.numel() * 4 <= ob || ob + nb <= mb, "mix overlaps out");
-  }
-  if (x.numel() == 0) return o;
-  mipipe::batch_mix(x.data_ptr(), o.data_ptr(), mix.data_ptr<float>(), (int)B, (int)C, (int)H,
-                    (int)W, is_f32(x), stream());
-  return o;
-}
-
-// number of rows whose argmax equals the label, accumulated into an int32 device counter
-Tensor top1_correct(Tensor logits, Tensor labels, optional<Tensor> out) {
-  check_act(logits, "logits");
-  check_cuda(labels, "labels");
-  c10::DeviceGuard g(logits.device());
-  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
-  TORCH_CHECK(logits.dim() == 2 && labels.numel() == logits.size(0), "top1 shape mismatch");
-  Tensor o;
-  if (out.has_value()) {
-    check_cuda(*out, "out");
-    TORCH_CHECK(out->scalar_type() == at::kInt && out->numel() == 1, "out must be one int32");
-    o = *out;
-  } else {
-    o = torch::zeros({1}, logits.options().dtype(at::kInt));
-  }
-  if (logits.size(0) > 0)
-    mipipe::top1_correct(logits.data_ptr(), labels.data_ptr<int64_t>(), (int)logits.size(0),
-                         (int)logits.size(1), o.data_ptr<int>(), stream(), is_f32(logits));
-  return o;
-}
-
-// Evaluation statistics of one batch (eval_stats.hip) accumulated into device buffers: counters
-// int64 [8], confusion int32 [Vv, Vv] (optional), hist int64 [3, bins] (optional, 1 <= bins <= 64).
-void eval_stats(Tensor logits, Tensor labels, Tensor counters, optional<Tensor> confusion,
-                optional<Tensor> hist, int64_t k, int64_t ignore_index, int64_t valid_cols) {
-  check_act(logits, "logits");
-  check_cuda(labels, "labels");
-  check_cuda(counters, "counters");
-  c10::DeviceGuard g(logits.device());
-  TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
-  TORCH_CHECK(logits.dim() == 2 && labels.numel() == logits.size(0), "eval_stats shape mismatch");
-  TORCH_CHECK(labels.device() == logits.device(), "labels must be on the logits' device");
-  TORCH_CHECK(counters.scalar_type() == at::kLong && counters.numel() == 8 &&
-              counters.device() == logits.device(),
-              "counters must be int64 [8] on the logits' device");
-  const int64_t R = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(R < (1ll << 31) - 4 && V < (1ll << 31), "eval_stats: logits too large");
-  const int64_t Vv = (valid_cols > 0 && valid_cols < V) ? valid_cols : V;
-  TORCH_CHECK(k >= 1 && k <= Vv, "k must be in [1, ", Vv, "], got ", k);
-  int* cm = nullptr;
-  if (confusion.has_value()) {
-    check_cuda(*confusion, "confusion");
-    TORCH_CHECK(confusion->scalar_type() == at::kInt && confusion->dim() == 2 &&
-                confusion->size(0) == Vv && confusion->size(1) == Vv &&
-                confusion->device() == logits.device(),
-                "confusion must be int32 [", Vv, ", ", Vv, "] on the logits' device");
-    cm = confusion->data_ptr<int>();
-  }
-  int64_t* hp = nullptr;
-  int64_t bins = 1;
-  if (hist.has_value()) {
-    check_cuda(*hist, "hist");
-    TORCH_CHECK(hist->scalar_type() == at::kLong && hist->dim() == 2 && hist->size(0) == 3 &&
-                hist->size(1) >= 1 && hist->size(1) <= 64 && hist->device() == logits.device(),
-                "hist must be int64 [3, bins] with 1 <= bins <= 64 on the logits' device");
-    bins = hist->size(1);
-    hp = hist->data_ptr<int64_t>();
-  }
-  if (R > 0)
-    mipipe::eval_stats(logits.data_ptr(), labels.data_ptr<int64_t>(), (int)R, (int)V, (int)Vv,
-                       (int)k, ignore_index, (int)bins, counters.data_ptr<int64_t>(), hp, cm,
-                       stream(), is_f32(logits));
-}
-
+// ------------------------------------------------------------------------------- optim
 // ---- flat-buffer kernels (csrc/kernels/optim.hip, ema.hip): the argument checks they share
 // p and every named state tensor: fp32, contiguous, on the GPU, p's size (a multiple of `align`),
 // 16-B aligned.  Returns the size.
@@ -1760,162 +1487,6 @@ void ema_buffers_swap(Tensor table, Tensor eb) {
   c10::DeviceGuard gd(eb.device());
   mipipe::ema_buffers_swap((const long*)table.data_ptr<int64_t>(), rows, eb.data_ptr<float>(),
                            eb.numel(), stream());
-}
-
-Tensor nchw_to_nhwc(Tensor x, at::ScalarType dtype, int64_t pad_to) {
-  check_cuda(x, "x");
-  c10::DeviceGuard g(x.device());
-  TORCH_CHECK(dtype == at::kBFloat16 || dtype == at::kFloat, "nchw_to_nhwc produces bf16 / fp32");
-  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, "x must be fp32/bf16");
-  TORCH_CHECK(x.dim() == 4, "x must be NCHW");
-  int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  int Cp = C;
-  if (pad_to > 0 && C % pad_to) Cp = (int)((C + pad_to - 1) / pad_to * pad_to);
-  Cp = (Cp + 7) / 8 * 8;
-  auto y = torch::empty({N, H, W, Cp}, x.options().dtype(dtype));
-  mipipe::nchw_to_nhwc(x.data_ptr(), x.scalar_type() == at::kBFloat16, y.data_ptr(), N, C, H, W, Cp,
-                       stream(), dtype == at::kFloat);
-  return y;
-}
-
-std::tuple<Tensor, Tensor> synthetic_batch(Tensor idx, int C, int H, int W, int classes, int seed,
-                                           at::ScalarType dtype) {
-  check_cuda(idx, "indices");
-  c10::DeviceGuard g(idx.device());
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "indices must be int64");
-  int n = idx.numel();
-  bool bf = dtype == at::kBFloat16;
-  TORCH_CHECK(bf || dtype == at::kFloat, "synthetic dtype must be fp32 or bf16");
-  auto x = torch::empty({n, C, H, W}, idx.options().dtype(dtype));
-  auto lab = torch::empty({n}, idx.options().dtype(at::kLong));
-  mipipe::synthetic_batch(idx.data_ptr<int64_t>(), n, C, H, W, classes, seed, x.data_ptr(), bf,
-                          lab.data_ptr<int64_t>(), stream());
-  return {x, lab};
-}
-
-// The record loader's crop / flip / normalise on the device: rec [n, label_bytes + C*H*W] uint8
-// whole records, idx [n] int64 sample indices, affine [2, C] fp32 -> (x [n,C,H,W], y [n] int64).
-std::tuple<Tensor, Tensor> record_decode(Tensor rec, Tensor idx, Tensor affine, int64_t C,
-                                         int64_t H, int64_t W, uint64_t seed, int64_t epoch,
-                                         int64_t pad, bool flip, bool train, int64_t label_bytes,
-                                         at::ScalarType dtype) {
-  check_cuda(rec, "rec");
-  check_cuda(idx, "idx");
-  check_f32(affine, "affine");
-  c10::DeviceGuard g(rec.device());
-  TORCH_CHECK(rec.scalar_type() == at::kByte, "rec must be uint8, got ", rec.scalar_type());
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64, got ", idx.scalar_type());
-  TORCH_CHECK(idx.device() == rec.device() && affine.device() == rec.device(),
-              "rec, idx and affine must be on one device");
-  const bool bf = dtype == at::kBFloat16;
-  TORCH_CHECK(bf || dtype == at::kFloat, "record_decode produces fp32 or bf16");
-  TORCH_CHECK(C >= 1 && H >= 1 && W >= 1 && C * H * W < (1ll << 31), "bad image shape");
-  TORCH_CHECK(label_bytes >= 1 && label_bytes <= 8, "label_bytes must be in [1, 8]");
-  TORCH_CHECK(pad >= 0 && pad < (1 << 20), "bad pad ", pad);
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == label_bytes + C * H * W, "rec must be [n, ",
-              label_bytes + C * H * W, "] (label bytes + C*H*W)");
-  const int64_t n = rec.size(0);
-  TORCH_CHECK(idx.dim() == 1 && idx.size(0) == n, "idx must be [n]");
-  TORCH_CHECK(affine.dim() == 2 && affine.size(0) == 2 && affine.size(1) == C,
-              "affine must be [2, C]");
-  auto x = torch::empty({n, C, H, W}, rec.options().dtype(dtype));
-  auto y = torch::empty({n}, rec.options().dtype(at::kLong));
-  if (n == 0) return {x, y};
-  mipipe::record_decode(rec.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), affine.data_ptr<float>(),
-                        x.data_ptr(), bf, y.data_ptr<int64_t>(), n, (int)C, (int)H, (int)W,
-                        (int)label_bytes, seed, (uint64_t)epoch, (int)pad, flip, train, stream());
-  return {x, y};
-}
-
-// The loader's "rrc" transform on the device (RandomResizedCrop / centre crop + bilinear resize
-// + flip + normalise): same inputs as record_decode, x is [n, C, Ho, Wo].
-std::tuple<Tensor, Tensor> record_decode_rrc(Tensor rec, Tensor idx, Tensor affine, int64_t C,
-                                             int64_t H, int64_t W, int64_t Ho, int64_t Wo,
-                                             uint64_t seed, int64_t epoch, bool flip, bool train,
-                                             int64_t label_bytes, at::ScalarType dtype) {
-  check_cuda(rec, "rec");
-  check_cuda(idx, "idx");
-  check_f32(affine, "affine");
-  c10::DeviceGuard g(rec.device());
-  TORCH_CHECK(rec.scalar_type() == at::kByte, "rec must be uint8, got ", rec.scalar_type());
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64, got ", idx.scalar_type());
-  TORCH_CHECK(idx.device() == rec.device() && affine.device() == rec.device(),
-              "rec, idx and affine must be on one device");
-  const bool bf = dtype == at::kBFloat16;
-  TORCH_CHECK(bf || dtype == at::kFloat, "record_decode_rrc produces fp32 or bf16");
-  TORCH_CHECK(C >= 1 && H >= 2 && W >= 2 && H <= 32768 && W <= 32768 &&
-                  C * H * W < (1ll << 31), "bad stored shape (H, W in [2, 32768])");
-  TORCH_CHECK(Ho >= 1 && Wo >= 1 && Ho + Wo <= mipipe::record_decode_rrc_max_extent_sum &&
-                  C * Ho * Wo < (1ll << 31),
-              "bad output size ", Ho, "x", Wo, " (positive, Ho + Wo <= ",
-              mipipe::record_decode_rrc_max_extent_sum, ")");
-  TORCH_CHECK(label_bytes >= 1 && label_bytes <= 8, "label_bytes must be in [1, 8]");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == label_bytes + C * H * W, "rec must be [n, ",
-              label_bytes + C * H * W, "] (label bytes + C*H*W)");
-  TORCH_CHECK(rec.is_contiguous() && idx.is_contiguous(), "rec and idx must be contiguous");
-  const int64_t n = rec.size(0);
-  TORCH_CHECK(idx.dim() == 1 && idx.size(0) == n, "idx must be [n]");
-  TORCH_CHECK(affine.dim() == 2 && affine.size(0) == 2 && affine.size(1) == C,
-              "affine must be [2, C]");
-  auto x = torch::empty({n, C, Ho, Wo}, rec.options().dtype(dtype));
-  auto y = torch::empty({n}, rec.options().dtype(at::kLong));
-  if (n == 0) return {x, y};
-  mipipe::record_decode_rrc(rec.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(),
-                            affine.data_ptr<float>(), x.data_ptr(), bf, y.data_ptr<int64_t>(), n,
-                            (int)C, (int)H, (int)W, (int)Ho, (int)Wo, (int)label_bytes, seed,
-                            (uint64_t)epoch, flip, train, stream());
-  return {x, y};
-}
-
-// TrivialAugmentWide of whole records on the device (augment.hip): rec [n, label_bytes + C*H*W]
-// uint8, idx [n] int64 -> a new record tensor of the same layout, for the decode kernels to read.
-// force < 0: the op is a hash of (seed, epoch, idx); else op | m << 8 | (sign is +) << 16.
-Tensor record_augment(Tensor rec, Tensor idx, int64_t C, int64_t H, int64_t W, uint64_t seed,
-                      int64_t epoch, int64_t label_bytes, int64_t force, int64_t parts) {
-  check_cuda(rec, "rec");
-  check_cuda(idx, "idx");
-  c10::DeviceGuard g(rec.device());
-  TORCH_CHECK(rec.scalar_type() == at::kByte, "rec must be uint8, got ", rec.scalar_type());
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64, got ", idx.scalar_type());
-  TORCH_CHECK(idx.device() == rec.device(), "rec and idx must be on one device");
-  TORCH_CHECK(C == 1 || C == 3, "record_augment needs 1 or 3 channels, got ", C);
-  TORCH_CHECK(H >= 1 && W >= 1 && H <= 32768 && W <= 32768 && C * H * W < (1ll << 31) - 16,
-              "bad image shape (H, W in [1, 32768])");
-  TORCH_CHECK(label_bytes >= 1 && label_bytes <= 8, "label_bytes must be in [1, 8]");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(1) == label_bytes + C * H * W, "rec must be [n, ",
-              label_bytes + C * H * W, "] (label bytes + C*H*W)");
-  TORCH_CHECK(rec.is_contiguous() && idx.is_contiguous(), "rec and idx must be contiguous");
-  const int64_t n = rec.size(0);
-  TORCH_CHECK(idx.dim() == 1 && idx.size(0) == n, "idx must be [n]");
-  TORCH_CHECK(mipipe_aug::force_ok(force), "bad force word ", force,
-              " (op | m << 8 | sign << 16, op < 14, m < 31)");
-  TORCH_CHECK(parts >= 0 && parts <= 64, "parts must be in [0, 64] (0: chosen by size)");
-  auto out = torch::empty_like(rec);
-  if (n == 0) return out;
-  mipipe::record_augment(rec.data_ptr<uint8_t>(), idx.data_ptr<int64_t>(), out.data_ptr<uint8_t>(),
-                         n, (int)C, (int)H, (int)W, (int)label_bytes, seed, (uint64_t)epoch,
-                         (long)force, (int)parts, stream());
-  return out;
-}
-
-// Random Erasing in place on the decoded batch x [n, C, Ho, Wo] (fp32 / bf16): the box of sample
-// idx[s] (a hash of seed, epoch and idx[s]; applied with probability pq / 2^24) becomes 0.0.
-Tensor batch_erase_(Tensor x, Tensor idx, uint64_t seed, int64_t epoch, int64_t pq) {
-  check_act(x, "x");
-  check_cuda(idx, "idx");
-  c10::DeviceGuard g(x.device());
-  TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64, got ", idx.scalar_type());
-  TORCH_CHECK(idx.device() == x.device(), "x and idx must be on one device");
-  TORCH_CHECK(x.dim() == 4, "x must be [n, C, Ho, Wo], got ", x.dim(), " dimensions");
-  const int64_t n = x.size(0), C = x.size(1), Ho = x.size(2), Wo = x.size(3);
-  TORCH_CHECK(Ho <= 32768 && Wo <= 32768 && C * Ho * Wo < (1ll << 31) - 4 * C * Ho,
-              "sample too large (Ho, Wo <= 32768, C*Ho*Wo < 2^31)");
-  TORCH_CHECK(idx.dim() == 1 && idx.size(0) == n && idx.is_contiguous(), "idx must be [n]");
-  TORCH_CHECK(pq >= 0 && pq <= (1 << 24), "pq must be in [0, 2^24], got ", pq);
-  if (x.numel() == 0 || pq == 0) return x;
-  mipipe::batch_erase(x.data_ptr(), is_f32(x), idx.data_ptr<int64_t>(), n, (int)C, (int)Ho,
-                      (int)Wo, seed, (uint64_t)epoch, (uint32_t)pq, stream());
-  return x;
 }
 
 // ------------------------------------------------------------------------------- transformer ops
@@ -2457,6 +2028,11 @@ Tensor avgpool2d_bwd(Tensor dy, std::vector<int64_t> xs, int64_t k, int64_t s, i
 
 }  // namespace
 
+namespace mipipe_bind {
+void bind_loss(py::module& m);  // csrc/bind/loss.cpp: cross-entropy, top-1, evaluation statistics
+void bind_data(py::module& m);  // csrc/bind/data.cpp: layout, synthetic data, records, batch mix
+}
+
 namespace mipipe_comm {
 void init_comm(py::module& m);  // csrc/comm/reducer.cpp: native DDP reducer, bf16 wire passes
 void init_oneshot(py::module& m);  // csrc/comm/oneshot.cpp: one-shot IPC collectives
@@ -2466,6 +2042,8 @@ PYBIND11_MODULE(_C, m) {
   m.doc() = "mipipe gfx950 (MI355X) HIP kernels";
   mipipe_comm::init_comm(m);
   mipipe_comm::init_oneshot(m);
+  mipipe_bind::bind_loss(m);
+  mipipe_bind::bind_data(m);
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
         py::arg("shift") = py::none(), py::arg("slab_sum") = py::none(),
         py::arg("slab_sq") = py::none(), py::arg("bias") = py::none(), py::arg("relu") = false,
@@ -2584,19 +2162,6 @@ PYBIND11_MODULE(_C, m) {
         py::arg("plan") = -1, py::arg("addend") = py::none(),
         py::arg("prefetch") = py::none());
   m.def("touch", &touch, py::arg("tensors"));
-  m.def("cross_entropy_fwd", &cross_entropy_fwd, py::arg("logits"), py::arg("labels"),
-        py::arg("smoothing") = 0.0, py::arg("ignore_index") = -100, py::arg("valid_cols") = -1);
-  m.def("cross_entropy_bwd", &cross_entropy_bwd, py::arg("logits"), py::arg("labels"),
-        py::arg("work"), py::arg("gout"), py::arg("smoothing") = 0.0,
-        py::arg("ignore_index") = -100, py::arg("valid_cols") = -1);
-  m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd, py::arg("logits"), py::arg("labels"),
-        py::arg("smoothing"), py::arg("ignore_index"), py::arg("valid_cols") = -1);
-  m.def("cross_entropy_mixed_fwd", &cross_entropy_mixed_fwd, py::arg("logits"), py::arg("labels"),
-        py::arg("mix"), py::arg("smoothing") = 0.0, py::arg("valid_cols") = -1);
-  m.def("cross_entropy_mixed_bwd", &cross_entropy_mixed_bwd, py::arg("logits"), py::arg("labels"),
-        py::arg("mix"), py::arg("work"), py::arg("gout"), py::arg("smoothing") = 0.0,
-        py::arg("valid_cols") = -1);
-  m.def("batch_mix", &batch_mix, py::arg("x"), py::arg("mix"), py::arg("out") = py::none());
   m.def("sgd_step", &sgd_step);
   m.def("adamw_step", &adamw_step, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"),
         py::arg("shadow"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
@@ -2620,23 +2185,6 @@ PYBIND11_MODULE(_C, m) {
         py::arg("calls_dev"), py::arg("every"), py::arg("w_min"), py::arg("warmup"));
   m.def("ema_buffers_swap", &ema_buffers_swap, py::arg("table"), py::arg("ema_buffers"));
   m.attr("EMA_ROW_MAX") = mipipe::kEmaRowMax;
-  m.def("nchw_to_nhwc", &nchw_to_nhwc);
-  m.def("synthetic_batch", &synthetic_batch);
-  m.def("record_decode", &record_decode, py::arg("rec"), py::arg("idx"), py::arg("affine"),
-        py::arg("C"), py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("epoch"),
-        py::arg("pad"), py::arg("flip"), py::arg("train"), py::arg("label_bytes"),
-        py::arg("dtype"));
-  m.def("record_decode_rrc", &record_decode_rrc, py::arg("rec"), py::arg("idx"),
-        py::arg("affine"), py::arg("C"), py::arg("H"), py::arg("W"), py::arg("Ho"), py::arg("Wo"),
-        py::arg("seed"), py::arg("epoch"), py::arg("flip"), py::arg("train"),
-        py::arg("label_bytes"), py::arg("dtype"));
-  m.def("record_augment", &record_augment, py::arg("rec"), py::arg("idx"), py::arg("C"),
-        py::arg("H"), py::arg("W"), py::arg("seed"), py::arg("epoch"), py::arg("label_bytes"),
-        py::arg("force") = -1, py::arg("parts") = 0);
-  m.def("record_augment_parts", &mipipe::record_augment_parts, py::arg("C"), py::arg("H"),
-        py::arg("W"));
-  m.def("batch_erase_", &batch_erase_, py::arg("x"), py::arg("idx"), py::arg("seed"),
-        py::arg("epoch"), py::arg("pq"));
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd", &gelu_bwd);
   m.def("gemm_gelu", &gemm_gelu, py::arg("a"), py::arg("b"), py::arg("bias") = py::none(),
@@ -2668,11 +2216,6 @@ PYBIND11_MODULE(_C, m) {
   m.def("stem_pack", &stem_pack, py::arg("x"), py::arg("pad"), py::arg("Hp"), py::arg("Wsp"),
         py::arg("dtype") = at::kBFloat16, py::arg("w") = py::none());
   m.def("stem_wgrad_unpack", &stem_wgrad_unpack, py::arg("dwp"), py::arg("g"));
-  m.def("top1_correct", &top1_correct, py::arg("logits"), py::arg("labels"),
-        py::arg("out") = py::none());
-  m.def("eval_stats", &eval_stats, py::arg("logits"), py::arg("labels"), py::arg("counters"),
-        py::arg("confusion") = py::none(), py::arg("hist") = py::none(), py::arg("k") = 5,
-        py::arg("ignore_index") = -100, py::arg("valid_cols") = -1);
   m.def("set_splitk_target", [](int v) { mipipe::g_splitk_target = std::max(1, v); });
   m.def("get_splitk_target", []() { return mipipe::g_splitk_target; });
   m.def("set_wgrad_xcd", [](bool on) { mipipe::g_wgrad_xcd = on ? 1 : 0; });

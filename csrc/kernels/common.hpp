@@ -222,4 +222,30 @@ __device__ __forceinline__ SplitPos splitk_pos(uint32_t xcd_splits) {
   return SplitPos{m.tile, m.split, xcd_splits};
 }
 
+// ---- host side ---------------------------------------------------------------------------------
+// blocks of 256 threads for `work` items, per_thread items each, at most cap (grid-stride kernels)
+inline int grid1d(long work, int per_thread = 1, int cap = 8192) {
+  long g = (work / per_thread + 255) / 256;
+  return (int)std::max<long>(1, std::min<long>(g, cap));
+}
+
+// Run-time choices into template arguments: the launchers call these with a generic lambda
+// instead of writing out an if / else ladder per combination.
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+// f(std::integral_constant<int, V>{}) for the V among Vs that equals v (none: nothing is called)
+template <int... Vs, class F>
+inline void dispatch_int(int v, F&& f) {
+  (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// f(T{}) for the activation dtype: T = float (f32) or __bf16
+template <class F>
+inline void dispatch_act(bool f32, F&& f) {
+  if (f32) f(float{});
+  else f(__bf16{});
+}
+
 }  // namespace mipipe

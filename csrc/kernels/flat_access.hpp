@@ -118,22 +118,12 @@ __device__ __forceinline__ void tile_walk(long n4, const float* const (&src)[NA]
   }
 }
 
-// ---- host side: run-time choices into template arguments ------------------------------------
+// ---- host side: the streaming bit into a template argument -----------------------------------
 inline bool flat_nt() { return (g_nt_store & 1024) != 0; }  // the one reader of the streaming bit
 
 template <class F>
-inline void dispatch_bool(bool b, F&& f) {
-  if (b) f(std::true_type{});
-  else f(std::false_type{});
-}
-template <class F>
 inline void dispatch_nt(F&& f) {
-  dispatch_bool(flat_nt(), f);
-}
-// f(std::integral_constant<int, V>{}) for the V among Vs that equals v (none: nothing is called)
-template <int... Vs, class F>
-inline void dispatch_int(int v, F&& f) {
-  (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  dispatch_bool(flat_nt(), f);  // common.hpp
 }
 
 }  // namespace mipipe

@@ -1,5 +1,5 @@
 // Host-side launch API of mipipe's gfx950 kernels (raw pointers + shapes + stream).
-// Bound to Python in csrc/bindings.cpp.  Every launcher is graph-capture safe: no
+// Bound to Python in csrc/bindings.cpp and csrc/bind/*.cpp.  Every launcher is graph-capture safe: no
 // allocation, no synchronisation (cdna_hip_programming.md Guideline 9).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -349,24 +349,18 @@ void avgpool_bwd(const void* dy, void* dx, int N, int HW, int C, hipStream_t st,
 void cross_entropy_fwd_bwd(const void* logits, const int64_t* labels, float* loss, void* grad,
                            int R, int V, float smoothing, int64_t ignore_index, int* work,
                            hipStream_t st, bool f32 = false, int valid_cols = 0);
-// The training-step split of the same loss: cross_entropy_fwd writes the loss, the valid-row count
-// (work[0]) and per-row losses / log-sum-exps (work + 4: [2][R] floats; work holds 4 + 2R ints);
-// cross_entropy_bwd then writes grad = (softmax - target) * gout[0] / count from the logits.
-void cross_entropy_fwd(const void* logits, const int64_t* labels, float* loss, int R, int V,
-                       float smoothing, int64_t ignore_index, int* work, hipStream_t st, bool f32,
-                       int Vv);
-void cross_entropy_bwd(const void* logits, const int64_t* labels, const int* work,
-                       const float* gout, void* grad, int R, int V, float smoothing,
-                       int64_t ignore_index, hipStream_t st, bool f32, int Vv);
-// Pair-target form of the split loss (Mixup / CutMix): row r's target is lambda on labels[r] and
-// 1 - lambda on labels[R-1-r], lambda = mix[0] read on the device by both kernels.  Every row
-// counts (no ignore_index); same work layout, same arithmetic as the hard-label kernels.
-void cross_entropy_mixed_fwd(const void* logits, const int64_t* labels, const float* mix,
-                             float* loss, int R, int V, float smoothing, int* work,
-                             hipStream_t st, bool f32, int Vv);
-void cross_entropy_mixed_bwd(const void* logits, const int64_t* labels, const float* mix,
-                             const int* work, const float* gout, void* grad, int R, int V,
-                             float smoothing, hipStream_t st, bool f32, int Vv);
+// The training-step split of the same loss (loss.hip): cross_entropy_fwd writes the loss, the
+// valid-row count (work[0]) and per-row losses / log-sum-exps (work + 4: [2][R] floats; work holds
+// 4 + 2R ints); cross_entropy_bwd then writes grad = (softmax - target) * gout[0] / count from the
+// logits.  mix != null: the pair-target form (Mixup / CutMix) — row r's target is lambda on
+// labels[r] and 1 - lambda on labels[R-1-r], lambda = mix[0] read on the device by both kernels;
+// every row counts (ignore_index is unused); same work layout, same arithmetic.
+void cross_entropy_fwd(const void* logits, const int64_t* labels, const float* mix, float* loss,
+                       int R, int V, float smoothing, int64_t ignore_index, int* work,
+                       hipStream_t st, bool f32, int Vv);
+void cross_entropy_bwd(const void* logits, const int64_t* labels, const float* mix,
+                       const int* work, const float* gout, void* grad, int R, int V,
+                       float smoothing, int64_t ignore_index, hipStream_t st, bool f32, int Vv);
 // Mixup / CutMix of x [B][C][H][W] with its reverse (mix.hip): sample i with sample B-1-i, as the
 // device descriptor mix (fp32[8]: lambda, mode, y0, y1, x0, x1) says.  out == x mixes in place.
 void batch_mix(const void* x, void* out, const float* mix, int B, int C, int H, int W, bool f32,

@@ -1,388 +1,17 @@
-// Memory-bound kernels of the training step: fused cross-entropy (fwd+bwd in one pass over
-// the logits), the DDP bf16 gradient wire, NCHW->NHWC input conversion, on-device synthetic data,
-// GELU, LayerNorm, embedding-grad scatter and column sums.  16-B vector accesses throughout
-// (cdna_hip_programming.md Guideline 13).  The optimizers live in optim.hip.
+// Memory-bound kernels of the training step: the DDP bf16 gradient wire, NCHW->NHWC input
+// conversion, on-device synthetic data, the cache-touch probe, GELU, LayerNorm, embedding-grad
+// scatter, column sums, dropout and the stem packing.  16-B vector accesses throughout
+// (cdna_hip_programming.md Guideline 13).  The loss lives in loss.hip, the optimizers in optim.hip.
 #include "common.hpp"
 #include "launchers.hpp"
 
 namespace mipipe {
 
-static int grid1d(long work, int per_thread = 1, int cap = 8192) {
-  long g = (work / per_thread + 255) / 256;
-  return (int)std::max<long>(1, std::min<long>(g, cap));
-}
-
-// ------------------------------------------------------------------------------ cross-entropy
-__global__ void ce_count_kernel(const int64_t* __restrict__ labels, int R, int64_t ignore,
-                                int* __restrict__ out) {
-  __shared__ int red[256];
-  int c = 0;
-  for (int i = threadIdx.x; i < R; i += 256) c += labels[i] != ignore;
-  red[threadIdx.x] = c;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0];
-}
-
-__device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
-  return r;
-}
-
-// one block per row; logits T (bf16 / fp32) [R][V] of which the first Vv columns are classes
-// (the rest: tile padding of the vocabulary, excluded from the softmax, gradient 0)
-template <class T>
-__global__ __launch_bounds__(256) void ce_kernel(const T* __restrict__ logits,
-                                                 const int64_t* __restrict__ labels,
-                                                 float* __restrict__ loss, T* __restrict__ grad,
-                                                 int V, int Vv, float eps, int64_t ignore,
-                                                 const int* __restrict__ nvalid,
-                                                 float* __restrict__ rowloss) {
-  __shared__ float sh[8];
-  const long row = blockIdx.x;
-  const T* x = logits + row * V;
-  T* g = grad + row * V;
-  const int64_t lab = labels[row];
-  const bool valid = lab != ignore;
-  const bool vec = (V % 8) == 0;
-  float mx = -INFINITY, sx = 0.f;
-  if (vec) {
-    for (int c = threadIdx.x; c < V / 8; c += 256) {
-      float v[8];
-      load8(x + c * 8, v);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        if (c * 8 + q < Vv) {
-          mx = fmaxf(mx, v[q]);
-          sx += v[q];
-        }
-      }
-    }
-  } else {
-    for (int c = threadIdx.x; c < Vv; c += 256) {
-      float v = (float)x[c];
-      mx = fmaxf(mx, v);
-      sx += v;
-    }
-  }
-  mx = block_reduce(mx, sh, true);
-  sx = block_reduce(sx, sh, false);
-  float se = 0.f;
-  if (vec) {
-    for (int c = threadIdx.x; c < V / 8; c += 256) {
-      float v[8];
-      load8(x + c * 8, v);
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (c * 8 + q < Vv) se += __expf(v[q] - mx);
-    }
-  } else {
-    for (int c = threadIdx.x; c < Vv; c += 256) se += __expf((float)x[c] - mx);
-  }
-  se = block_reduce(se, sh, false);
-  const float lse = mx + __logf(se);
-  const float inv_n = 1.f / (float)max(1, nvalid[0]);
-  if (threadIdx.x == 0) {  // summed in a fixed order by ce_sum_kernel (no float atomics)
-    float l = 0.f;
-    if (valid) {
-      float xl = (float)x[lab];
-      l = (1.f - eps) * (lse - xl) + eps * (lse - sx / (float)Vv);
-    }
-    rowloss[row] = l * inv_n;
-  }
-  const float scale = valid ? inv_n : 0.f;
-  const float inv_se = 1.f / se;
-  const float base_t = eps / (float)Vv;
-  if (vec) {
-    for (int c = threadIdx.x; c < V / 8; c += 256) {
-      float v[8];
-      load8(x + c * 8, v);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        int col = c * 8 + q;
-        float t = base_t + (col == lab ? 1.f - eps : 0.f);
-        v[q] = col < Vv ? (__expf(v[q] - mx) * inv_se - t) * scale : 0.f;
-      }
-      store8(g + c * 8, v);
-    }
-  } else {
-    for (int c = threadIdx.x; c < V; c += 256) {
-      float t = base_t + (c == lab ? 1.f - eps : 0.f);
-      g[c] = (T)(c < Vv ? (__expf((float)x[c] - mx) * inv_se - t) * scale : 0.f);
-    }
-  }
-}
-
-// loss = sum of the per-row losses in a fixed order (thread t: rows t, t+256, ...; then a tree)
-__global__ __launch_bounds__(256) void ce_sum_kernel(const float* __restrict__ rowloss, int R,
-                                                     float* __restrict__ loss) {
-  __shared__ float red[256];
-  float a = 0.f;
-  for (int i = threadIdx.x; i < R; i += 256) a += rowloss[i];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *loss = red[0];
-}
-
-void cross_entropy_fwd_bwd(const void* logits, const int64_t* labels, float* loss, void* grad,
-                           int R, int V, float smoothing, int64_t ignore_index, int* work,
-                           hipStream_t st, bool f32, int Vv) {
-  if (Vv <= 0 || Vv > V) Vv = V;
-  float* rowloss = reinterpret_cast<float*>(work + 4);
-  hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(256), 0, st, labels, R, ignore_index, work);
-  if (f32)
-    hipLaunchKernelGGL(ce_kernel<float>, dim3(R), dim3(256), 0, st, (const float*)logits, labels,
-                       loss, (float*)grad, V, Vv, smoothing, ignore_index, (const int*)work, rowloss);
-  else
-    hipLaunchKernelGGL(ce_kernel<__bf16>, dim3(R), dim3(256), 0, st, (const __bf16*)logits, labels,
-                       loss, (__bf16*)grad, V, Vv, smoothing, ignore_index, (const int*)work, rowloss);
-  hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(256), 0, st, rowloss, R, loss);
-}
-
-// Split form for the training step: the forward keeps only the per-row log-sum-exp (one pass
-// over the logits: running max and rescaled exp-sum per thread, merged per wave and block), the
-// backward writes grad = (softmax - target) * g / n straight from the logits with the upstream
-// gradient g read on the device — so no [R][V] gradient is written in the forward and then
-// rescaled by a separate elementwise pass (BERT-base MLM: 640 x 30528 logits).
-__device__ __forceinline__ void lse_merge(float& m, float& s, float mo, float so) {
-  const float mn = fmaxf(m, mo);
-  if (mn == -INFINITY) return;  // both empty
-  s = s * __expf(m - mn) + so * __expf(mo - mn);
-  m = mn;
-}
-
-// MIX: the pair-target form (Mixup / CutMix).  Row r has the labels a = labels[r] and
-// b = labels[R-1-r] with weights lambda = mix[0] and 1 - lambda, read on the device; every row
-// counts (nvalid and ignore are unused).  lambda = 1 gives the hard-label result bit for bit:
-// 1 * x[a] + 0 * x[b] is x[a], and (1 - eps) * (1 * [c==a] + 0 * [c==b]) is 1 - eps or 0.
-template <class T, bool MIX = false>
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logits,
-                                                     const int64_t* __restrict__ labels, int V,
-                                                     int Vv, float eps, int64_t ignore,
-                                                     const int* __restrict__ nvalid,
-                                                     float* __restrict__ rowloss,
-                                                     float* __restrict__ lse_out,
-                                                     const float* __restrict__ mix = nullptr) {
-  __shared__ float sh[3][4];
-  const long row = blockIdx.x;
-  const T* x = logits + row * V;
-  float m = -INFINITY, s = 0.f, sx = 0.f;
-  if ((V % 8) == 0) {
-    for (int c = threadIdx.x; c < V / 8; c += 256) {
-      float v[8];
-      load8(x + c * 8, v);
-      float m8 = -INFINITY;
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (c * 8 + q < Vv) {
-          m8 = fmaxf(m8, v[q]);
-          sx += v[q];
-        }
-      const float mn = fmaxf(m, m8);
-      if (mn == -INFINITY) continue;
-      float e = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-        if (c * 8 + q < Vv) e += __expf(v[q] - mn);
-      s = s * __expf(m - mn) + e;
-      m = mn;
-    }
-  } else {
-    for (int c = threadIdx.x; c < Vv; c += 256) {
-      const float v = (float)x[c];
-      sx += v;
-      lse_merge(m, s, v, 1.f);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float mo = __shfl_xor(m, o), so = __shfl_xor(s, o);
-    lse_merge(m, s, mo, so);
-    sx += __shfl_xor(sx, o);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][w] = m;
-    sh[1][w] = s;
-    sh[2][w] = sx;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sh[0][0], S = sh[1][0], SX = sh[2][0];
-    for (int i = 1; i < 4; ++i) {
-      lse_merge(M, S, sh[0][i], sh[1][i]);
-      SX += sh[2][i];
-    }
-    const float lse = M + __logf(S);
-    const int64_t lab = labels[row];
-    bool valid = lab != ignore;
-    float xl = 0.f;
-    int n;
-    if constexpr (MIX) {
-      const int64_t lab2 = labels[(long)gridDim.x - 1 - row];
-      const float lam = mix[0], om = 1.f - lam;
-      // a label outside the classes reads nothing (its logit counts as 0)
-      const float xa = (uint64_t)lab < (uint64_t)Vv ? (float)x[lab] : 0.f;
-      const float xb = (uint64_t)lab2 < (uint64_t)Vv ? (float)x[lab2] : 0.f;
-      xl = lam * xa + om * xb;
-      valid = true;
-      n = (int)gridDim.x;
-    } else {
-      if (valid) xl = (float)x[lab];
-      n = nvalid[0];
-    }
-    float l = 0.f;
-    if (valid) l = (1.f - eps) * (lse - xl) + eps * (lse - SX / (float)Vv);
-    rowloss[row] = l / (float)max(1, n);
-    lse_out[row] = lse;
-  }
-}
-
-// grid (column blocks, rows): 8 columns per thread (V % 8 == 0) or 1
-// the target of column col: eps / Vv + (1 - eps) on the label, or, pair-target, (1 - eps) times
-// lambda on label a plus 1 - lambda on label b
-template <bool MIX>
-__device__ __forceinline__ float ce_target(int col, int64_t lab, int64_t lab2, float lam,
-                                           float om, float base_t, float eps) {
-  if constexpr (MIX)
-    return base_t + (1.f - eps) * ((col == lab ? lam : 0.f) + (col == lab2 ? om : 0.f));
-  else
-    return base_t + (col == lab ? 1.f - eps : 0.f);
-}
-
-template <class T, bool VEC, bool MIX = false>
-__global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logits,
-                                                     const int64_t* __restrict__ labels,
-                                                     const float* __restrict__ lse,
-                                                     const int* __restrict__ nvalid,
-                                                     const float* __restrict__ gout,
-                                                     T* __restrict__ grad, int R, int V, int Vv,
-                                                     float eps, int64_t ignore,
-                                                     const float* __restrict__ mix = nullptr) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= (VEC ? V / 8 : V)) return;
-  const float gs = gout[0] / (float)max(1, MIX ? R : nvalid[0]), base_t = eps / (float)Vv;
-  float lam = 1.f, om = 0.f;
-  if constexpr (MIX) {
-    lam = mix[0];
-    om = 1.f - lam;
-  }
-  for (long row = blockIdx.y; row < R; row += gridDim.y) {  // (grid.y is capped at 65535)
-  const int64_t lab = labels[row];
-  const int64_t lab2 = MIX ? labels[R - 1 - row] : lab;
-  const float scale = (MIX || lab != ignore) ? gs : 0.f;
-  const float l = lse[row];
-  if constexpr (VEC) {
-    float v[8];
-    load8(logits + row * V + c * 8, v);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int col = c * 8 + q;
-      const float t = ce_target<MIX>(col, lab, lab2, lam, om, base_t, eps);
-      v[q] = col < Vv ? (__expf(v[q] - l) - t) * scale : 0.f;
-    }
-    store8(grad + row * V + c * 8, v);
-  } else {
-    const float t = ce_target<MIX>(c, lab, lab2, lam, om, base_t, eps);
-    grad[row * V + c] = (T)(c < Vv ? (__expf((float)logits[row * V + c] - l) - t) * scale : 0.f);
-  }
-  }
-}
-
-void cross_entropy_fwd(const void* logits, const int64_t* labels, float* loss, int R, int V,
-                       float smoothing, int64_t ignore_index, int* work, hipStream_t st, bool f32,
-                       int Vv) {
-  if (Vv <= 0 || Vv > V) Vv = V;
-  float* rowloss = reinterpret_cast<float*>(work + 4);
-  float* lse = rowloss + R;
-  hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(256), 0, st, labels, R, ignore_index, work);
-  if (f32)
-    hipLaunchKernelGGL(ce_fwd_kernel<float>, dim3(R), dim3(256), 0, st, (const float*)logits,
-                       labels, V, Vv, smoothing, ignore_index, (const int*)work, rowloss, lse);
-  else
-    hipLaunchKernelGGL(ce_fwd_kernel<__bf16>, dim3(R), dim3(256), 0, st, (const __bf16*)logits,
-                       labels, V, Vv, smoothing, ignore_index, (const int*)work, rowloss, lse);
-  hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(256), 0, st, rowloss, R, loss);
-}
-
-void cross_entropy_bwd(const void* logits, const int64_t* labels, const int* work,
-                       const float* gout, void* grad, int R, int V, float smoothing,
-                       int64_t ignore_index, hipStream_t st, bool f32, int Vv) {
-  if (Vv <= 0 || Vv > V) Vv = V;
-  const float* lse = reinterpret_cast<const float*>(work + 4) + R;
-  const bool vec = V % 8 == 0;
-  const dim3 g((unsigned)(((vec ? V / 8 : V) + 255) / 256), (unsigned)std::min(R, 65535));
-  auto go = [&](auto t, auto vec_c) {
-    using T = decltype(t);
-    hipLaunchKernelGGL((ce_bwd_kernel<T, decltype(vec_c)::value>), g, dim3(256), 0, st,
-                       (const T*)logits, labels, lse, work, gout, (T*)grad, R, V, Vv,
-                       smoothing, ignore_index);
-  };
-  if (f32) {
-    if (vec) go(float(), std::true_type());
-    else go(float(), std::false_type());
-  } else {
-    if (vec) go(__bf16(), std::true_type());
-    else go(__bf16(), std::false_type());
-  }
-}
-
-void cross_entropy_mixed_fwd(const void* logits, const int64_t* labels, const float* mix,
-                             float* loss, int R, int V, float smoothing, int* work,
-                             hipStream_t st, bool f32, int Vv) {
-  if (Vv <= 0 || Vv > V) Vv = V;
-  float* rowloss = reinterpret_cast<float*>(work + 4);
-  float* lse = rowloss + R;
-  if (f32)
-    hipLaunchKernelGGL((ce_fwd_kernel<float, true>), dim3(R), dim3(256), 0, st,
-                       (const float*)logits, labels, V, Vv, smoothing, (int64_t)0,
-                       (const int*)nullptr, rowloss, lse, mix);
-  else
-    hipLaunchKernelGGL((ce_fwd_kernel<__bf16, true>), dim3(R), dim3(256), 0, st,
-                       (const __bf16*)logits, labels, V, Vv, smoothing, (int64_t)0,
-                       (const int*)nullptr, rowloss, lse, mix);
-  hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(256), 0, st, rowloss, R, loss);
-}
-
-void cross_entropy_mixed_bwd(const void* logits, const int64_t* labels, const float* mix,
-                             const int* work, const float* gout, void* grad, int R, int V,
-                             float smoothing, hipStream_t st, bool f32, int Vv) {
-  if (Vv <= 0 || Vv > V) Vv = V;
-  const float* lse = reinterpret_cast<const float*>(work + 4) + R;
-  const bool vec = V % 8 == 0;
-  const dim3 g((unsigned)(((vec ? V / 8 : V) + 255) / 256), (unsigned)std::min(R, 65535));
-  auto go = [&](auto t, auto vec_c) {
-    using T = decltype(t);
-    hipLaunchKernelGGL((ce_bwd_kernel<T, decltype(vec_c)::value, true>), g, dim3(256), 0, st,
-                       (const T*)logits, labels, lse, (const int*)nullptr, gout, (T*)grad, R, V,
-                       Vv, smoothing, (int64_t)0, mix);
-  };
-  if (f32) {
-    if (vec) go(float(), std::true_type());
-    else go(float(), std::false_type());
-  } else {
-    if (vec) go(__bf16(), std::true_type());
-    else go(__bf16(), std::false_type());
-  }
-}
-
-// ------------------------------------------------------------------------------ cache warming
-// One 4-B load per 64-B line of up to kTouchRanges byte ranges: brings a GEMM operand that was
-// last read milliseconds ago (a weight, a saved activation) into the memory-side cache before
-// its GEMM runs (mipipe/ops/prefetch.py launches it on a side stream beside the previous GEMM).
+// ------------------------------------------------------------------------------ cache touch
+// One 4-B load per 64-B line of up to kTouchRanges byte ranges: brings tensors that were last
+// read milliseconds ago (a weight, a saved activation) into the memory-side cache.  A probe for
+// tests and tools: the training step warms a GEMM's operands from the previous GEMM's own blocks
+// (TouchRanges in gemm.hip); launching this kernel on a side stream was measured and dropped.
 // Nothing is written: the loads feed a sum that is stored only if it equals a constant AND sink
 // is non-null (never, sink is null) — which keeps the compiler from dropping them.
 __global__ __launch_bounds__(256) void touch_kernel(TouchRanges r, uint32_t* __restrict__ sink) {
@@ -403,57 +32,6 @@ void touch(const TouchRanges& r, hipStream_t st) {
   for (int k = 0; k < r.count; ++k) lines = std::max(lines, r.bytes[k] >> 6);
   if (lines == 0) return;
   hipLaunchKernelGGL(touch_kernel, dim3(grid1d(lines, 1, 512)), dim3(256), 0, st, r, nullptr);
-}
-
-// ------------------------------------------------------------------------------ evaluation
-// Top-1 correct count (the reference's eval loop: argmax over classes == label, summed): one
-// wave per row, first maximal index wins (torch.argmax's tie rule), NaN counts as maximal; the
-// per-block count is one integer atomic into *correct (order-independent, so deterministic).
-template <class T>
-__global__ __launch_bounds__(256) void top1_correct_kernel(const T* __restrict__ logits,
-                                                           const int64_t* __restrict__ labels,
-                                                           int R, int V, int* __restrict__ correct) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + wave;
-  int hit = 0;
-  if (row < R) {
-    const T* x = logits + (long)row * V;
-    float best = -INFINITY;
-    int arg = 0x7fffffff;
-    for (int c = lane; c < V; c += 64) {
-      const float v = (float)x[c];
-      if (v > best || (v != v && best == best)) {  // strictly greater keeps the first index
-        best = v;
-        arg = c;
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o);
-      const int oa = __shfl_xor(arg, o);
-      const bool onan = ob != ob, mnan = best != best;
-      if ((onan && !mnan) || (onan == mnan && (ob > best || (ob == best && oa < arg)))) {
-        best = ob;
-        arg = oa;
-      }
-    }
-    hit = (lane == 0 && (int64_t)arg == labels[row]) ? 1 : 0;
-  }
-  __shared__ int cnt;
-  if (threadIdx.x == 0) cnt = 0;
-  __syncthreads();
-  if (hit) atomicAdd(&cnt, 1);
-  __syncthreads();
-  if (threadIdx.x == 0 && cnt) atomicAdd(correct, cnt);
-}
-
-void top1_correct(const void* logits, const int64_t* labels, int R, int V, int* correct,
-                  hipStream_t st, bool f32) {
-  dim3 g((R + 3) / 4);
-  if (f32)
-    hipLaunchKernelGGL(top1_correct_kernel<float>, g, dim3(256), 0, st, (const float*)logits, labels, R, V, correct);
-  else
-    hipLaunchKernelGGL(top1_correct_kernel<__bf16>, g, dim3(256), 0, st, (const __bf16*)logits, labels, R, V, correct);
 }
 
 // ------------------------------------------------------------------------------ DDP wire format
@@ -530,13 +108,13 @@ void nchw_to_nhwc(const void* x, bool x_is_bf16, void* y, int N, int C, int H, i
                   hipStream_t st, bool y_f32) {
   long total = (long)N * H * W;
   dim3 g(grid1d(total));
-  if (y_f32) {
-    if (x_is_bf16) hipLaunchKernelGGL((nchw_to_nhwc_kernel<true, float>), g, dim3(256), 0, st, x, (float*)y, N, C, H, W, Cp);
-    else hipLaunchKernelGGL((nchw_to_nhwc_kernel<false, float>), g, dim3(256), 0, st, x, (float*)y, N, C, H, W, Cp);
-  } else {
-    if (x_is_bf16) hipLaunchKernelGGL((nchw_to_nhwc_kernel<true, __bf16>), g, dim3(256), 0, st, x, (__bf16*)y, N, C, H, W, Cp);
-    else hipLaunchKernelGGL((nchw_to_nhwc_kernel<false, __bf16>), g, dim3(256), 0, st, x, (__bf16*)y, N, C, H, W, Cp);
-  }
+  dispatch_act(y_f32, [&](auto t) {
+    using T = decltype(t);
+    dispatch_bool(x_is_bf16, [&](auto in_bf16) {
+      hipLaunchKernelGGL((nchw_to_nhwc_kernel<decltype(in_bf16)::value, T>), g, dim3(256), 0, st,
+                         x, (T*)y, N, C, H, W, Cp);
+    });
+  });
 }
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
@@ -791,12 +369,11 @@ void colsum_f32(const void* x, bool bf16, float* out, long rows, int cols, float
   colsum_grid(rows, cols, G, rpb);
   dim3 grid((cols + kColsumChunk - 1) / kColsumChunk, (unsigned)G);
   // work != null (deterministic mode): per-row-block partial rows, then a fixed-order sum
-  if (bf16)
-    hipLaunchKernelGGL(colsum_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16*)x, out, rows,
-                       cols, rpb, work);
-  else
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, st, (const float*)x, out, rows,
-                       cols, rpb, work);
+  dispatch_act(!bf16, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, st, (const T*)x, out, rows, cols, rpb,
+                       work);
+  });
   if (work != nullptr) det_sum_rows(work, nullptr, (int)G, cols, out, nullptr, true, st);
 }
 
@@ -1319,30 +896,22 @@ void layernorm_fwd(const void* x, const void* res, const float* gamma, const flo
   ln_exact_shape(H, vec, nc);
   // forward: the 8-wide exact kernel measured slower than the generic one at H = 1024 (9.5 vs
   // 8.0 us, 4096 rows, profiles/r6_layernorm_modes.txt); the 4-wide one is faster at H = 768
-  if (vec == 4) {
-    auto go = [&](auto drop_c, auto vec_c, auto nc_c) {
-      constexpr bool DROP = decltype(drop_c)::value;
-      constexpr int VEC = decltype(vec_c)::value, NC = decltype(nc_c)::value;
-      hipLaunchKernelGGL((layernorm_fwd_exact_kernel<DROP, VEC, NC>), dim3((rows + 3) / 4),
-                         dim3(256), 0, st, (const __bf16*)x, (const __bf16*)res, gamma, beta,
-                         (__bf16*)y, (__bf16*)xsum, mean, rstd, rows, eps, dr);
-    };
-    auto go_v = [&](auto drop_c) {  // (4, 1) H = 256, (4, 3) H = 768
-      if (nc == 1) go(drop_c, std::integral_constant<int, 4>(), std::integral_constant<int, 1>());
-      else go(drop_c, std::integral_constant<int, 4>(), std::integral_constant<int, 3>());
-    };
-    if (dr.thr != 0u) go_v(std::true_type());
-    else go_v(std::false_type());
-    return;
-  }
-  if (dr.thr != 0u)
-    hipLaunchKernelGGL(layernorm_fwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st,
+  dispatch_bool(dr.thr != 0u, [&](auto drop_c) {
+    constexpr bool DROP = decltype(drop_c)::value;
+    if (vec == 4) {
+      // (4, 1) H = 256, else (4, 3) H = 768: one of the two always launches
+      dispatch_int<1, 3>(nc == 1 ? 1 : 3, [&](auto nc_c) {
+        hipLaunchKernelGGL((layernorm_fwd_exact_kernel<DROP, 4, decltype(nc_c)::value>),
+                           dim3((rows + 3) / 4), dim3(256), 0, st, (const __bf16*)x,
+                           (const __bf16*)res, gamma, beta, (__bf16*)y, (__bf16*)xsum, mean, rstd,
+                           rows, eps, dr);
+      });
+      return;
+    }
+    hipLaunchKernelGGL(layernorm_fwd_kernel<DROP>, dim3((rows + 3) / 4), dim3(256), 0, st,
                        (const __bf16*)x, (const __bf16*)res, gamma, beta, (__bf16*)y,
                        (__bf16*)xsum, mean, rstd, rows, H, eps, dr);
-  else
-    hipLaunchKernelGGL(layernorm_fwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st,
-                       (const __bf16*)x, (const __bf16*)res, gamma, beta, (__bf16*)y,
-                       (__bf16*)xsum, mean, rstd, rows, H, eps, dr);
+  });
 }
 
 // dx = rstd*(g*γ - mean(g*γ) - x̂*mean(g*γ*x̂)); per-block partials of Σg·x̂ and Σg for dγ, dβ.
@@ -1616,55 +1185,33 @@ void layernorm_bwd(const void* dy, const void* x, const float* mean, const float
   const bool dp = dr.thr != 0u && dxd != nullptr;
   int vec, nc;
   ln_exact_shape(H, vec, nc);
-  if (vec != 0) {
-    auto go = [&](auto vec_c, auto nc_c, auto w_c, auto drop_c, auto bsum_c) {
-      constexpr int VEC = decltype(vec_c)::value, NC = decltype(nc_c)::value;
-      constexpr int W = decltype(w_c)::value;
+  dispatch_bool(dp, [&](auto drop_c) {
+    dispatch_bool(wd != nullptr, [&](auto bsum_c) {
       constexpr bool DROP = decltype(drop_c)::value, BSUM = decltype(bsum_c)::value;
-      hipLaunchKernelGGL((layernorm_bwd_exact_kernel<VEC, NC, W, DROP, BSUM>), dim3(G),
-                         dim3(W * 64), 0, st, (const __bf16*)dy, (const __bf16*)x, mean, rstd,
-                         gamma, (__bf16*)dx, wg, wb, rows, rpb, (__bf16*)dxd, dr, wd);
-    };
-    auto go_w = [&](auto vec_c, auto nc_c, auto drop_c, auto bsum_c) {
-      if (g_ln_mode == 4) go(vec_c, nc_c, std::integral_constant<int, 4>(), drop_c, bsum_c);
-      else if (g_ln_mode == 8) go(vec_c, nc_c, std::integral_constant<int, 8>(), drop_c, bsum_c);
-      else go(vec_c, nc_c, std::integral_constant<int, 16>(), drop_c, bsum_c);
-    };
-    auto go_s = [&](auto drop_c, auto bsum_c) {
-      using I8 = std::integral_constant<int, 8>;
-      using I4 = std::integral_constant<int, 4>;
-      if (vec == 8 && nc == 1) go_w(I8(), std::integral_constant<int, 1>(), drop_c, bsum_c);
-      else if (vec == 8) go_w(I8(), std::integral_constant<int, 2>(), drop_c, bsum_c);
-      else if (nc == 1) go_w(I4(), std::integral_constant<int, 1>(), drop_c, bsum_c);
-      else go_w(I4(), std::integral_constant<int, 3>(), drop_c, bsum_c);
-    };
-    auto go_d = [&](auto drop_c) {
-      if (wd != nullptr) go_s(drop_c, std::true_type());
-      else go_s(drop_c, std::false_type());
-    };
-    if (dp) go_d(std::true_type());
-    else go_d(std::false_type());
-    det_sum_rows(wg, wb, G, H, dgamma, dbeta, true, st, wd, dbias);
-    return;
-  }
-  auto go = [&](auto nch, auto drop_c, auto bsum_c) {
-    constexpr int NCH = decltype(nch)::value;
-    constexpr bool DROP = decltype(drop_c)::value, BSUM = decltype(bsum_c)::value;
-    hipLaunchKernelGGL((layernorm_bwd_kernel<NCH, DROP, BSUM>), dim3(G), dim3(256), 0, st,
-                       (const __bf16*)dy, (const __bf16*)x, mean, rstd, gamma, (__bf16*)dx, wg,
-                       wb, rows, H, rpb, (__bf16*)dxd, dr, wd);
-  };
-  auto go_b = [&](auto nch, auto drop_c) {
-    if (wd != nullptr) go(nch, drop_c, std::true_type());
-    else go(nch, drop_c, std::false_type());
-  };
-  if (H <= 1024) {
-    if (dp) go_b(std::integral_constant<int, 2>(), std::true_type());
-    else go_b(std::integral_constant<int, 2>(), std::false_type());
-  } else {
-    if (dp) go_b(std::integral_constant<int, LN_MAXC>(), std::true_type());
-    else go_b(std::integral_constant<int, LN_MAXC>(), std::false_type());
-  }
+      if (vec != 0) {
+        // the exact shapes as 10 * VEC + NC: (8, 1) H = 512, else (8, 2) 1024; (4, 1) 256, else
+        // (4, 3) 768 — every (vec, nc) maps to a listed shape, so a kernel always launches;
+        // waves per block from the mode: 4, 8, else 16
+        const int waves = g_ln_mode == 4 || g_ln_mode == 8 ? g_ln_mode : 16;
+        const int shape = vec == 8 ? (nc == 1 ? 81 : 82) : (nc == 1 ? 41 : 43);
+        dispatch_int<81, 82, 41, 43>(shape, [&](auto shape_c) {
+          constexpr int VEC = decltype(shape_c)::value / 10, NC = decltype(shape_c)::value % 10;
+          dispatch_int<4, 8, 16>(waves, [&](auto w_c) {
+            constexpr int W = decltype(w_c)::value;
+            hipLaunchKernelGGL((layernorm_bwd_exact_kernel<VEC, NC, W, DROP, BSUM>), dim3(G),
+                               dim3(W * 64), 0, st, (const __bf16*)dy, (const __bf16*)x, mean,
+                               rstd, gamma, (__bf16*)dx, wg, wb, rows, rpb, (__bf16*)dxd, dr, wd);
+          });
+        });
+        return;
+      }
+      dispatch_int<2, LN_MAXC>(H <= 1024 ? 2 : LN_MAXC, [&](auto nch_c) {
+        hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(nch_c)::value, DROP, BSUM>), dim3(G),
+                           dim3(256), 0, st, (const __bf16*)dy, (const __bf16*)x, mean, rstd,
+                           gamma, (__bf16*)dx, wg, wb, rows, H, rpb, (__bf16*)dxd, dr, wd);
+      });
+    });
+  });
   det_sum_rows(wg, wb, G, H, dgamma, dbeta, true, st, wd, dbias);
 }
 
@@ -1768,13 +1315,13 @@ void stem_pack(const void* x, bool x_is_bf16, void* y, int N, int C, int H, int 
     wk.w = w; wk.wp = wp; wk.Co = Co; wk.K = K;
     wk.s0 = ws[0]; wk.s1 = ws[1]; wk.s2 = ws[2]; wk.s3 = ws[3];
   }
-  if (y_f32) {
-    if (x_is_bf16) hipLaunchKernelGGL((stem_pack_kernel<true, float>), g, dim3(256), 0, st, x, (float*)y, N, C, H, W, pad, Hp, Wsp, wk);
-    else hipLaunchKernelGGL((stem_pack_kernel<false, float>), g, dim3(256), 0, st, x, (float*)y, N, C, H, W, pad, Hp, Wsp, wk);
-  } else {
-    if (x_is_bf16) hipLaunchKernelGGL((stem_pack_kernel<true, __bf16>), g, dim3(256), 0, st, x, (__bf16*)y, N, C, H, W, pad, Hp, Wsp, wk);
-    else hipLaunchKernelGGL((stem_pack_kernel<false, __bf16>), g, dim3(256), 0, st, x, (__bf16*)y, N, C, H, W, pad, Hp, Wsp, wk);
-  }
+  dispatch_act(y_f32, [&](auto t) {
+    using T = decltype(t);
+    dispatch_bool(x_is_bf16, [&](auto in_bf16) {
+      hipLaunchKernelGGL((stem_pack_kernel<decltype(in_bf16)::value, T>), g, dim3(256), 0, st, x,
+                         (T*)y, N, C, H, W, pad, Hp, Wsp, wk);
+    });
+  });
 }
 
 // Stem filter gradient, kernel layout [Co][K][K2][8] -> ACCUMULATED into the parameter's

@@ -26,11 +26,6 @@ namespace mipipe {
 
 namespace {
 
-int grid1d(long work, int per_thread = 1, int cap = 8192) {
-  long g = (work / per_thread + 255) / 256;
-  return (int)std::max<long>(1, std::min<long>(g, cap));
-}
-
 // SGD ([torch] optim/sgd.py:354-380): g += wd*p; m = momentum*m + (1-damp)*g (m = g first);
 // p -= lr * (nesterov ? g + momentum*m : m).  n % 4 == 0.  Cached accesses, a plain grid-stride
 // loop; the momentum load stays behind mom != 0 because m aliases the gradient buffer when the

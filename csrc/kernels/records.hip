@@ -225,6 +225,17 @@ void launch_rrc(const uint8_t* rec, const int64_t* idx, const float* affine, voi
                      epoch, (int)flip, (int)train, parts);
 }
 
+// f(T{}, V) for the output dtype and the widest row vector that divides the output width w:
+// 16 bytes (8 bf16 / 4 fp32), else 4 elements, else 1
+template <class F>
+void dispatch_row_vec(bool bf16_out, int w, F&& f) {
+  dispatch_act(!bf16_out, [&](auto t) {
+    constexpr int VMAX = 16 / (int)sizeof(t);
+    dispatch_int<VMAX, 4, 1>(w % VMAX == 0 ? VMAX : w % 4 == 0 ? 4 : 1,
+                             [&](auto v_c) { f(t, v_c); });
+  });
+}
+
 }  // namespace
 
 void record_decode_rrc(const uint8_t* rec, const int64_t* idx, const float* affine, void* x,
@@ -232,31 +243,20 @@ void record_decode_rrc(const uint8_t* rec, const int64_t* idx, const float* affi
                        int label_bytes, uint64_t seed, uint64_t epoch, bool flip, bool train,
                        hipStream_t st) {
   if (n <= 0) return;
-#define MIPIPE_RRC(T, V) \
-  launch_rrc<T, V>(rec, idx, affine, x, y, n, C, H, W, Ho, Wo, label_bytes, seed, epoch, flip, train, st)
-  if (bf16_out) {
-    if (Wo % 8 == 0) MIPIPE_RRC(__bf16, 8);
-    else if (Wo % 4 == 0) MIPIPE_RRC(__bf16, 4);
-    else MIPIPE_RRC(__bf16, 1);
-  } else {
-    if (Wo % 4 == 0) MIPIPE_RRC(float, 4);
-    else MIPIPE_RRC(float, 1);
-  }
-#undef MIPIPE_RRC
+  dispatch_row_vec(bf16_out, Wo, [&](auto t, auto v_c) {
+    launch_rrc<decltype(t), decltype(v_c)::value>(rec, idx, affine, x, y, n, C, H, W, Ho, Wo,
+                                                  label_bytes, seed, epoch, flip, train, st);
+  });
 }
 
 void record_decode(const uint8_t* rec, const int64_t* idx, const float* affine, void* x,
                    bool bf16_out, int64_t* y, long n, int C, int H, int W, int label_bytes,
                    uint64_t seed, uint64_t epoch, int pad, bool flip, bool train, hipStream_t st) {
   if (n <= 0) return;
-  if (bf16_out) {
-    if (W % 8 == 0) launch<__bf16, 8>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
-    else if (W % 4 == 0) launch<__bf16, 4>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
-    else launch<__bf16, 1>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
-  } else {
-    if (W % 4 == 0) launch<float, 4>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
-    else launch<float, 1>(rec, idx, affine, x, y, n, C, H, W, label_bytes, seed, epoch, pad, flip, train, st);
-  }
+  dispatch_row_vec(bf16_out, W, [&](auto t, auto v_c) {
+    launch<decltype(t), decltype(v_c)::value>(rec, idx, affine, x, y, n, C, H, W, label_bytes,
+                                              seed, epoch, pad, flip, train, st);
+  });
 }
 
 }  // namespace mipipe

@@ -43,8 +43,8 @@ def _newest_header() -> float:
 def sources_digest(kind: str) -> str:
     """SHA-256 over the sources (paths + bytes) a library is built from."""
     if kind == "C":
-        pats = ["kernels/*.hip", "kernels/*.hpp", "bindings.cpp", "comm/*.cpp", "comm/*.h*",
-                "common/*.h*"]
+        pats = ["kernels/*.hip", "kernels/*.hpp", "bindings.cpp", "bind/*.cpp", "bind/*.hpp",
+                "comm/*.cpp", "comm/*.h*", "common/*.h*"]
     else:
         pats = ["runtime/*.cpp", "runtime/*.h*", "common/*.h*"]  # common/: host + device headers
     files = sorted({f for p in pats for f in glob.glob(os.path.join(CSRC, p))})
@@ -119,7 +119,9 @@ def build_kernels(jobs: int = 8, force: bool = False, verbose: bool = True) -> s
     hip_flags = common + [f"--offload-arch={ARCH}", "-munsafe-fp-atomics"] + tflags
     cpp_flags = common + tflags
     srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
-    cpps = [os.path.join(CSRC, "bindings.cpp")] + sorted(glob.glob(os.path.join(CSRC, "comm", "*.cpp")))
+    cpps = [os.path.join(CSRC, "bindings.cpp")] + \
+        sorted(glob.glob(os.path.join(CSRC, "bind", "*.cpp"))) + \
+        sorted(glob.glob(os.path.join(CSRC, "comm", "*.cpp")))
     hdr = _newest_header()
     jobs_list = []
     for s in srcs:
