@@ -408,7 +408,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_kernel(BwdArgs a) {
         pdrop = kp ? p * inv_keep : 0.f;
         dpv = kp ? dpv * inv_keep : 0.f;
       }
-      const bool valid = (it * 32 + qi) < S;
+      // a row whose every key is masked with -inf has lse = -inf (O = 0): p above is NaN
+      // (-inf + inf); the row contributes nothing, as a select like the out-of-range rows
+      const bool valid = (it * 32 + qi) < S && lsel[qi] != -INFINITY;
       pd[i] = valid ? pdrop : 0.f;
       ds[i] = valid ? p * (dpv - dell[qi]) * a.scale : 0.f;
     }

@@ -1300,7 +1300,9 @@ def attention(qkv: Tensor, batch: int, seq: int, heads: int, mask: Optional[Tens
 
     qkv [B*S, 3*H*D] (q | k | v column blocks, head-major), mask [B, S] additive key bias
     (0 / -inf style) -> o [B*S, H*D], ready for the output projection.  ``p_drop`` is the
-    attention-probability dropout (keyed by ``seed``; recomputed in the backward)."""
+    attention-probability dropout (keyed by ``seed``; recomputed in the backward).  A sample whose
+    every key is masked with -inf (an all-padding row of a batch) yields zero output and zero
+    gradient, not NaN."""
     D = qkv.shape[-1] // (3 * heads)
     if scale is None:
         scale = 1.0 / math.sqrt(D)
