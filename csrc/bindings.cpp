@@ -1567,7 +1567,7 @@ std::tuple<Tensor, Tensor, Tensor, optional<Tensor>> layernorm_fwd(Tensor x, Ten
 std::tuple<Tensor, optional<Tensor>, optional<Tensor>, optional<Tensor>> layernorm_bwd(
     Tensor dy, Tensor x, Tensor mean, Tensor rstd, Tensor gamma, optional<Tensor> dgamma_acc,
     optional<Tensor> dbeta_acc, double drop_p, int64_t drop_seed,
-    optional<Tensor> drop_seed_dev, optional<Tensor> dbias_acc) {
+    optional<Tensor> drop_seed_dev, optional<Tensor> dbias_acc, optional<Tensor> dsum) {
   check_bf16(dy, "dy");
   check_bf16(x, "x");
   c10::DeviceGuard g(x.device());
@@ -1598,10 +1598,17 @@ std::tuple<Tensor, optional<Tensor>, optional<Tensor>, optional<Tensor>> layerno
   const mipipe::DropSpec ds{(float)drop_p, (uint32_t)drop_seed,
                             (const uint32_t*)i32_dev(drop_seed_dev, "drop_seed_dev")};
   if (drop_p > 0.0) dxd = torch::empty_like(x);
+  // dsum: the residual stream's gradient (pre-LN blocks), added to dx before its one rounding
+  if (dsum.has_value()) {
+    check_bf16(*dsum, "dsum");
+    TORCH_CHECK(dsum->sizes() == x.sizes() && dsum->device() == x.device(),
+                "dsum must have dx's shape and device");
+    TORCH_CHECK(drop_p == 0.0, "layernorm_bwd: dsum is not combined with the fused dropout");
+  }
   mipipe::layernorm_bwd(dy.data_ptr(), x.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
                         gamma.data_ptr<float>(), dx.data_ptr(), pg, pb, work.data_ptr<float>(),
                         rows, (int)H, stream(), dxd.has_value() ? dxd->data_ptr() : nullptr,
-                        drop_p > 0.0 ? &ds : nullptr, pd);
+                        drop_p > 0.0 ? &ds : nullptr, pd, ptr_or_null(dsum));
   return {dx, dg, db, dxd};
 }
 
@@ -2031,6 +2038,7 @@ Tensor avgpool2d_bwd(Tensor dy, std::vector<int64_t> xs, int64_t k, int64_t s, i
 namespace mipipe_bind {
 void bind_loss(py::module& m);  // csrc/bind/loss.cpp: cross-entropy, top-1, evaluation statistics
 void bind_data(py::module& m);  // csrc/bind/data.cpp: layout, synthetic data, records, batch mix
+void bind_vit(py::module& m);   // csrc/bind/vit.cpp: patchify, token assembly
 }
 
 namespace mipipe_comm {
@@ -2044,6 +2052,7 @@ PYBIND11_MODULE(_C, m) {
   mipipe_comm::init_oneshot(m);
   mipipe_bind::bind_loss(m);
   mipipe_bind::bind_data(m);
+  mipipe_bind::bind_vit(m);
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
         py::arg("shift") = py::none(), py::arg("slab_sum") = py::none(),
         py::arg("slab_sq") = py::none(), py::arg("bias") = py::none(), py::arg("relu") = false,
@@ -2196,7 +2205,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("x"), py::arg("mean"),
         py::arg("rstd"), py::arg("gamma"), py::arg("dgamma") = py::none(),
         py::arg("dbeta") = py::none(), py::arg("drop_p") = 0.0, py::arg("drop_seed") = 0,
-        py::arg("drop_seed_dev") = py::none(), py::arg("dbias") = py::none());
+        py::arg("drop_seed_dev") = py::none(), py::arg("dbias") = py::none(),
+        py::arg("dsum") = py::none());
   m.def("embedding_bwd", &embedding_bwd, py::arg("dy"), py::arg("idx"), py::arg("num_rows"),
         py::arg("out") = py::none(), py::arg("ordered") = false, py::arg("scale") = 1.0,
         py::arg("sorted_ids") = py::none(), py::arg("perm") = py::none());

@@ -365,6 +365,17 @@ void cross_entropy_bwd(const void* logits, const int64_t* labels, const float* m
 // device descriptor mix (fp32[8]: lambda, mode, y0, y1, x0, x1) says.  out == x mixes in place.
 void batch_mix(const void* x, void* out, const float* mix, int B, int C, int H, int W, bool f32,
                hipStream_t st);
+// Vision Transformer input side (vit.hip).  patchify: x [B, C, H, W] -> out [B*(H/P)*(W/P), C*P*P],
+// column (c, u, v) = conv_proj.weight.view(D, -1)'s; H % P == W % P == P % 8 == 0, 16-byte aligned.
+void patchify(const void* x, void* out, int B, int C, int H, int W, int P, bool in_f32,
+              bool out_f32, hipStream_t st);
+// h [B*(N+1), D]: row (b, 0) = cls + pos[0], row (b, 1 + n) = e[b*N + n] + pos[1 + n]; D % 8 == 0
+void tokens_assemble_fwd(const void* e, const float* cls, const float* pos, void* h, int B, int N,
+                         int D, bool f32, hipStream_t st);
+// de [B*N, D] = dh without the class rows; dpos [(N+1)*D] += sum_b dh[b], dcls [D] += sum_b dh[b, 0]
+// (ascending b, one owner per element: the same bits in every run)
+void tokens_assemble_bwd(const void* dh, void* de, float* dpos, float* dcls, int B, int N, int D,
+                         bool f32, hipStream_t st);
 // *correct += #rows whose first maximal logit is at the label (torch.argmax tie rule)
 void top1_correct(const void* logits, const int64_t* labels, int R, int V, int* correct,
                   hipStream_t st, bool f32 = false);
@@ -530,10 +541,13 @@ void layernorm_fwd(const void* x, const void* res, const float* gamma, const flo
                    void* xsum, float* mean, float* rstd, long rows, int H, float eps,
                    hipStream_t st, const DropSpec* drop = nullptr);
 // drop + dxd: also writes dxd = dropout'(dx), the dropped branch's gradient
+// dsum (like dx; not with drop): dx = bf16(dx_ln + dsum), the sum rounded once — a pre-LN block's
+// stream gradient added in the LayerNorm's own pass; dbias then sums that stored total
 void layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd,
                    const float* gamma, void* dx, float* dgamma, float* dbeta, float* work,
                    long rows, int H, hipStream_t st, void* dxd = nullptr,
-                   const DropSpec* drop = nullptr, float* dbias = nullptr);
+                   const DropSpec* drop = nullptr, float* dbias = nullptr,
+                   const void* dsum = nullptr);
 int layernorm_bwd_blocks(long rows);  // partial rows of layernorm_bwd's work
 // LayerNorm kernel family: 0 = the generic one-row-per-wave kernels (16-B chunks, any H % 8 == 0),
 // 4 / 8 (default) / 16 = the exact-width kernels (chunk width picked so every lane holds whole

@@ -921,7 +921,10 @@ void layernorm_fwd(const void* x, const void* res, const float* gamma, const flo
 // DROP: also dxd = dropout'(dx) — the gradient of the dropped branch (the residual keeps dx).
 // BSUM: also per-block partials of Σ_rows of the branch gradient (dxd, else dx; bf16-rounded as
 // stored) — the bias gradient of the Linear that produced the LayerNorm's input.
-template <int NCH, bool DROP, bool BSUM>
+// ADD (not with DROP): dx = bf16(dx_ln + dsum) — the gradient of a pre-LN block's residual stream,
+// which the normalised sum also carries on, added before the one rounding; BSUM then sums that
+// stored total (in a pre-LN block exactly the producing Linear's output gradient).
+template <int NCH, bool DROP, bool BSUM, bool ADD>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const __bf16* __restrict__ dy,
                                                             const __bf16* __restrict__ x,
                                                             const float* __restrict__ mean,
@@ -932,7 +935,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const __bf16* __rest
                                                             float* __restrict__ pb, long rows,
                                                             int H, int rows_per_block,
                                                             __bf16* __restrict__ dxd, DropArgs dr,
-                                                            float* __restrict__ pd) {
+                                                            float* __restrict__ pd,
+                                                            const __bf16* __restrict__ dsum) {
+  static_assert(!(DROP && ADD), "the stream addend is not combined with the fused dropout");
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint32_t dbase = DROP ? drop_base(dr.seed, dr.seed_dev) : 0u;
   const int nc = H / 8;
@@ -948,7 +953,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const __bf16* __rest
   }
   const long r0 = (long)blockIdx.x * rows_per_block;
   const long r1 = min(rows, r0 + rows_per_block);
-  uint4 ng[NCH], nx[NCH];
+  uint4 ng[NCH], nx[NCH], ns[ADD ? NCH : 1];
   float nmu = 0.f, nrs = 0.f;
   auto fetch = [&](long row) {
 #pragma unroll
@@ -957,6 +962,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const __bf16* __rest
       if (c < nc) {
         ng[k] = *reinterpret_cast<const uint4*>(dy + row * H + c * 8);
         nx[k] = *reinterpret_cast<const uint4*>(x + row * H + c * 8);
+        if constexpr (ADD) ns[k] = *reinterpret_cast<const uint4*>(dsum + row * H + c * 8);
       }
     }
     nmu = mean[row];
@@ -965,12 +971,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const __bf16* __rest
   if (r0 + w < r1) fetch(r0 + w);
   for (long row = r0 + w; row < r1; row += 4) {
     const float mu = nmu, rs = nrs;
-    float g[NCH][8], xh[NCH][8];
+    float g[NCH][8], xh[NCH][8], sg[ADD ? NCH : 1][8];
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       if (lane + k * 64 < nc) {
         unpack8(ng[k], g[k]);
         unpack8(nx[k], xh[k]);
+        if constexpr (ADD) unpack8(ns[k], sg[k]);
       }
     }
     if (row + 4 < r1) fetch(row + 4);
@@ -998,6 +1005,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const __bf16* __rest
         float o[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) o[q] = rs * (g[k][q] * gam[k][q] - s1 - xh[k][q] * s2);
+        if constexpr (ADD) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) o[q] += sg[k][q];
+        }
         const uint4 ob = pack8(o);
         *reinterpret_cast<uint4*>(dx + row * H + c * 8) = ob;
         if constexpr (DROP) {  // from the bf16-rounded dx, as the standalone kernel would see it
@@ -1048,12 +1059,17 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const __bf16* __rest
 // through the one-row prefetch.  Partials: LDS, summed over the waves in a fixed pairwise order.
 // BERT-base 4096 x 768 with dropout + bias sum: 14.6 -> 11.3 us incl. the partial-row sum
 // (W = 16: 11.5, and 23.6 at H = 1024; profiles/r6_layernorm_modes.txt).
-template <int VEC, int NC, int W, bool DROP, bool BSUM>
+template <int VEC, int NC, int W, bool DROP, bool BSUM, bool ADD>
 __global__ __launch_bounds__(W * 64) void layernorm_bwd_exact_kernel(
     const __bf16* __restrict__ dy, const __bf16* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, __bf16* __restrict__ dx,
     float* __restrict__ pg, float* __restrict__ pb, long rows, int rows_per_block,
-    __bf16* __restrict__ dxd, DropArgs dr, float* __restrict__ pd) {
+    __bf16* __restrict__ dxd, DropArgs dr, float* __restrict__ pd,
+    const __bf16* __restrict__ dsum) {
+  static_assert(!(DROP && ADD), "the stream addend is not combined with the fused dropout");
+  // the addend's row is prefetched with dy / x, except in the 16-wave block: its 128 VGPRs have
+  // no room for a third row in flight, and 16 waves hide a load issued where it is used
+  constexpr bool PRE = ADD && W != 16;
   using VT = LnVec<VEC>;
   constexpr int H = NC * 64 * VEC;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1068,13 +1084,14 @@ __global__ __launch_bounds__(W * 64) void layernorm_bwd_exact_kernel(
     }
   const long r0 = (long)blockIdx.x * rows_per_block;
   const long r1 = min(rows, r0 + rows_per_block);
-  VT ng[NC], nx[NC];
+  VT ng[NC], nx[NC], ns[PRE ? NC : 1];
   float nmu = 0.f, nrs = 0.f;
   auto fetch = [&](long row) {
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
       ng[k] = reinterpret_cast<const VT*>(dy + row * H)[lane + k * 64];
       nx[k] = reinterpret_cast<const VT*>(x + row * H)[lane + k * 64];
+      if constexpr (PRE) ns[k] = reinterpret_cast<const VT*>(dsum + row * H)[lane + k * 64];
     }
     nmu = mean[row];
     nrs = rstd[row];
@@ -1082,11 +1099,12 @@ __global__ __launch_bounds__(W * 64) void layernorm_bwd_exact_kernel(
   if (r0 + w < r1) fetch(r0 + w);
   for (long row = r0 + w; row < r1; row += W) {
     const float mu = nmu, rs = nrs;
-    float g[NC][VEC], xh[NC][VEC];
+    float g[NC][VEC], xh[NC][VEC], sg[PRE ? NC : 1][VEC];
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
       unpackv(ng[k], g[k]);
       unpackv(nx[k], xh[k]);
+      if constexpr (PRE) unpackv(ns[k], sg[k]);
     }
     if (row + W < r1) fetch(row + W);
     float s1 = 0.f, s2 = 0.f;
@@ -1109,6 +1127,15 @@ __global__ __launch_bounds__(W * 64) void layernorm_bwd_exact_kernel(
       float o[VEC];
 #pragma unroll
       for (int q = 0; q < VEC; ++q) o[q] = rs * (g[k][q] * gam[k][q] - s1 - xh[k][q] * s2);
+      if constexpr (PRE) {
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) o[q] += sg[k][q];
+      } else if constexpr (ADD) {
+        float t[VEC];
+        unpackv(reinterpret_cast<const VT*>(dsum + row * H)[c], t);
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) o[q] += t[q];
+      }
       const VT ob = packv<VT>(o);
       reinterpret_cast<VT*>(dx + row * H)[c] = ob;
       if constexpr (DROP) {  // from the bf16-rounded dx, as the standalone kernel would see it
@@ -1172,7 +1199,7 @@ int layernorm_bwd_blocks(long rows) {
 void layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd,
                    const float* gamma, void* dx, float* dgamma, float* dbeta, float* work,
                    long rows, int H, hipStream_t st, void* dxd, const DropSpec* drop,
-                   float* dbias) {
+                   float* dbias, const void* dsum) {
   // dgamma / dbeta (and dbias) are ACCUMULATED into (zeroed buffers or the flat gradient views)
   // from the per-block partial rows in work ([2 or 3][layernorm_bwd_blocks(rows)][H])
   int G, rpb;
@@ -1185,9 +1212,11 @@ void layernorm_bwd(const void* dy, const void* x, const float* mean, const float
   const bool dp = dr.thr != 0u && dxd != nullptr;
   int vec, nc;
   ln_exact_shape(H, vec, nc);
-  dispatch_bool(dp, [&](auto drop_c) {
+  // variant: 0 plain, 1 fused dropout, 2 stream addend (the host refuses dropout with an addend)
+  dispatch_int<0, 1, 2>(dp ? 1 : dsum != nullptr ? 2 : 0, [&](auto var_c) {
     dispatch_bool(wd != nullptr, [&](auto bsum_c) {
-      constexpr bool DROP = decltype(drop_c)::value, BSUM = decltype(bsum_c)::value;
+      constexpr bool DROP = decltype(var_c)::value == 1, ADD = decltype(var_c)::value == 2;
+      constexpr bool BSUM = decltype(bsum_c)::value;
       if (vec != 0) {
         // the exact shapes as 10 * VEC + NC: (8, 1) H = 512, else (8, 2) 1024; (4, 1) 256, else
         // (4, 3) 768 — every (vec, nc) maps to a listed shape, so a kernel always launches;
@@ -1198,17 +1227,19 @@ void layernorm_bwd(const void* dy, const void* x, const float* mean, const float
           constexpr int VEC = decltype(shape_c)::value / 10, NC = decltype(shape_c)::value % 10;
           dispatch_int<4, 8, 16>(waves, [&](auto w_c) {
             constexpr int W = decltype(w_c)::value;
-            hipLaunchKernelGGL((layernorm_bwd_exact_kernel<VEC, NC, W, DROP, BSUM>), dim3(G),
+            hipLaunchKernelGGL((layernorm_bwd_exact_kernel<VEC, NC, W, DROP, BSUM, ADD>), dim3(G),
                                dim3(W * 64), 0, st, (const __bf16*)dy, (const __bf16*)x, mean,
-                               rstd, gamma, (__bf16*)dx, wg, wb, rows, rpb, (__bf16*)dxd, dr, wd);
+                               rstd, gamma, (__bf16*)dx, wg, wb, rows, rpb, (__bf16*)dxd, dr, wd,
+                               (const __bf16*)dsum);
           });
         });
         return;
       }
       dispatch_int<2, LN_MAXC>(H <= 1024 ? 2 : LN_MAXC, [&](auto nch_c) {
-        hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(nch_c)::value, DROP, BSUM>), dim3(G),
+        hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(nch_c)::value, DROP, BSUM, ADD>), dim3(G),
                            dim3(256), 0, st, (const __bf16*)dy, (const __bf16*)x, mean, rstd,
-                           gamma, (__bf16*)dx, wg, wb, rows, H, rpb, (__bf16*)dxd, dr, wd);
+                           gamma, (__bf16*)dx, wg, wb, rows, H, rpb, (__bf16*)dxd, dr, wd,
+                           (const __bf16*)dsum);
       });
     });
   });

@@ -458,7 +458,9 @@ def layernorm_fwd(x: Tensor, gamma: Tensor, beta: Tensor, eps: float,
 
 
 def layernorm_bwd(dy: Tensor, x: Tensor, mean: Tensor, rstd: Tensor,
-                  gamma: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+                  gamma: Tensor, dsum: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """``dsum`` (dx's shape): the gradient of the residual stream a pre-LN block carries past the
+    LayerNorm, added to dx before its one rounding; dgamma / dbeta do not depend on it."""
     H = x.shape[-1]
     xf = _f(x).reshape(-1, H)
     g = _f(dy).reshape(-1, H)
@@ -467,7 +469,46 @@ def layernorm_bwd(dy: Tensor, x: Tensor, mean: Tensor, rstd: Tensor,
     dbeta = g.sum(0)
     gg = g * _f(gamma)
     dx = rstd.reshape(-1, 1) * (gg - gg.mean(-1, keepdim=True) - xhat * (gg * xhat).mean(-1, keepdim=True))
+    if dsum is not None:
+        dx = dx + _f(dsum).reshape(-1, H)
     return dx.reshape(x.shape).to(dy.dtype), dgamma, dbeta
+
+
+# ---- Vision Transformer input side (csrc/kernels/vit.hip)
+def patchify(x: Tensor, patch: int, dtype: torch.dtype) -> Tensor:
+    """x [B, C, H, W] -> [B*gh*gw, C*P*P] in ``dtype``: row (b, i, j), column (c, u, v) holds
+    ``x[b, c, i*P + u, j*P + v]`` — the column order of ``conv_proj.weight.view(D, C*P*P)``, so the
+    P x P stride-P convolution is ``rows @ weight.view(D, -1).T``.  A permutation and a cast."""
+    B, C, H, W = x.shape
+    P = int(patch)
+    if P < 1 or H % P or W % P:
+        raise ValueError(f"image {H}x{W} is not a whole number of {P}x{P} patches")
+    gh, gw = H // P, W // P
+    t = x.reshape(B, C, gh, P, gw, P).permute(0, 2, 4, 1, 3, 5)
+    return t.reshape(B * gh * gw, C * P * P).to(dtype)
+
+
+def tokens_assemble_fwd(e: Tensor, cls: Tensor, pos: Tensor) -> Tensor:
+    """e [B*N, D] (activation dtype), cls [D], pos [(N+1)*D] (master precision) ->
+    h [B*(N+1), D]: ``h[b, 0] = cls + pos[0]``, ``h[b, 1+n] = e[b, n] + pos[1+n]``; one add in the
+    master precision, one rounding to e's dtype."""
+    D = cls.numel()
+    S = pos.numel() // D
+    B = e.shape[0] // (S - 1)
+    pos = _f(pos).reshape(S, D)
+    h = torch.empty(B, S, D, dtype=pos.dtype, device=e.device)
+    h[:, 0] = _f(cls).reshape(D) + pos[0]
+    h[:, 1:] = _f(e).reshape(B, S - 1, D) + pos[1:]
+    return h.reshape(B * S, D).to(e.dtype)
+
+
+def tokens_assemble_bwd(dh: Tensor, batch: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """dh [B*(N+1), D] -> (de [B*N, D] = dh without the class rows, dpos [(N+1)*D] = Σ_b dh[b],
+    dcls [D] = Σ_b dh[b, 0]); the sums in fp32 (fp64 for fp64 input)."""
+    D = dh.shape[-1]
+    g = dh.reshape(batch, -1, D)
+    dpos = _f(g).sum(0)
+    return g[:, 1:].reshape(-1, D).contiguous(), dpos.reshape(-1), dpos[0].clone()
 
 
 _M32 = 0xFFFFFFFF

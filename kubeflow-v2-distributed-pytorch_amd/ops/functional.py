@@ -10,7 +10,9 @@ backward, SGD step) decomposes into these units, each one or two HIP launches:
   also produces the residual gradient;
 * :func:`linear`, :func:`cross_entropy`, :func:`cross_entropy_mixed` (the pair-target loss of
   Mixup / CutMix), :func:`max_pool2d`, :func:`global_avg_pool`, :func:`layer_norm`,
-  :func:`gelu`, :func:`attention`, :func:`embedding`.
+  :func:`gelu`, :func:`attention`, :func:`embedding`;
+* :func:`patchify`, :func:`tokens_assemble` and :func:`add_layer_norm` — the Vision Transformer's
+  patch rows, its token assembly and the pre-LN residual stream kept inside the LayerNorm kernels.
 
 Master weights stay fp32 (``nn.Parameter``); kernels consume a compute-dtype *shadow*
 (bf16 on the GPU) passed as a separate, non-differentiable argument; weight gradients come
@@ -1084,6 +1086,9 @@ class _LinearFn(Function):
                 dw = K.gemm(dy2, x2, True, False, None, "none", gdt)
                 if w_c.shape[0] != ctx.weight.shape[0]:
                     dw = dw[: ctx.weight.shape[0]]
+                if dw.dim() != ctx.weight.dim():
+                    # a parameter whose operand is its [out, -1] view (ViT's conv_proj filter)
+                    dw = dw.reshape(ctx.weight.shape)
                 if sink is not None:  # write it into the flat gradient now, report it ready
                     from mipipe.optim.flat import flat_space_for
                     fs = flat_space_for(ctx.weight)
@@ -1260,6 +1265,94 @@ def layer_norm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-12,
                 else int(dropout_seed) & 0xFFFFFFFF
             drop = (float(dropout_p), seed)
     return _LayerNormFn.apply(x, gamma, beta, eps, residual, res_give, drop, bias_slot)
+
+
+class _AddLayerNormFn(Function):
+    """(LN(x + residual), x + residual) with BOTH results differentiable: a pre-LN block
+    normalises the sum and carries it on as the residual stream."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, eps, bias_slot):
+        y, mean, rstd, xs = K.layernorm_fwd(x, gamma, beta, eps, residual)
+        ctx.save_for_backward(xs, mean, rstd, gamma)
+        ctx.beta = beta
+        ctx.bias_slot = bias_slot
+        ctx.set_materialize_grads(False)  # an unused stream output: no addend, not a zero tensor
+        return y, xs
+
+    @staticmethod
+    def backward(ctx, dy, dxs):
+        xs, mean, rstd, gamma = ctx.saved_tensors
+        if dy is None:  # only the stream is used: the sum's gradient passes through
+            return dxs, dxs, None, None, None, None
+        acc = None
+        if K.use_native(dy) and ctx.needs_input_grad[2] and ctx.needs_input_grad[3]:
+            tg, tb = _direct_grad_target(gamma), _direct_grad_target(ctx.beta)
+            if tg is not None and tb is not None:
+                acc = (tg[1], tb[1])
+        slot, tbias = ctx.bias_slot, None
+        if acc is not None and slot is not None and slot.bias is not None:
+            tbias = _direct_grad_target(slot.bias, xs.shape[-1])
+        # one pass: the LayerNorm's gradient plus the stream's, rounded once; that total is the
+        # gradient of x and of the residual alike (and what the producing Linear's bias sums)
+        dx, dgamma, dbeta, _ = K.layernorm_bwd(dy.contiguous(), xs, mean, rstd, gamma, acc, None,
+                                               None if tbias is None else tbias[1], dsum=dxs)
+        if tbias is not None:
+            slot.done = True
+        if acc is not None:
+            fs = _direct_grad_target(gamma)[0]
+            fs.grad_ready(gamma)
+            fs.grad_ready(ctx.beta)
+            return dx, dx, None, None, None, None
+        return dx, dx, dgamma.to(gamma.dtype), dbeta.to(gamma.dtype), None, None
+
+
+def add_layer_norm(x: Tensor, residual: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-6,
+                   bias_slot: Optional[BiasGradSlot] = None) -> Tuple[Tensor, Tensor]:
+    """``(y, xs)`` with ``xs = x + residual`` and ``y = LN(xs)`` — the pre-LN residual stream: the
+    forward kernel that normalises the sum also stores it, and the backward adds the stream's
+    gradient (``xs``'s) to the LayerNorm's in its own pass (one rounding of the total), so a
+    block's closing add runs as no launch of its own in either direction.  The total is the
+    gradient of ``x`` and of ``residual``.  ``bias_slot``: as :func:`layer_norm`."""
+    return _AddLayerNormFn.apply(x, residual, gamma, beta, eps, bias_slot)
+
+
+def patchify(x: Tensor, patch: int, dtype: torch.dtype) -> Tensor:
+    """The image as the patch embedding's GEMM operand: x [B, C, H, W] -> [B*gh*gw, C*P*P] in
+    ``dtype`` (:func:`mipipe.ops.kernels.patchify`).  The image takes no gradient."""
+    if x.requires_grad:
+        raise ValueError("patchify has no backward: the input image takes no gradient")
+    return K.patchify(x, patch, dtype)
+
+
+class _TokensAssembleFn(Function):
+    @staticmethod
+    def forward(ctx, e, cls, pos):
+        ctx.cls, ctx.pos = cls, pos
+        ctx.batch = e.shape[0] // (pos.numel() // cls.numel() - 1)
+        return K.tokens_assemble_fwd(e, cls.detach().reshape(-1), pos.detach().reshape(-1))
+
+    @staticmethod
+    def backward(ctx, dh):
+        cls, pos = ctx.cls, ctx.pos
+        tp = tc = None
+        if K.use_native(dh) and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
+            tp, tc = _direct_grad_target(pos), _direct_grad_target(cls)
+        if tp is not None and tc is not None:
+            de, _, _ = K.tokens_assemble_bwd(dh, ctx.batch, tp[1].reshape(-1), tc[1].reshape(-1))
+            tp[0].grad_ready(pos)
+            tc[0].grad_ready(cls)
+            return de, None, None
+        de, dpos, dcls = K.tokens_assemble_bwd(dh, ctx.batch)
+        return de, dcls.reshape(cls.shape).to(cls.dtype), dpos.reshape(pos.shape).to(pos.dtype)
+
+
+def tokens_assemble(e: Tensor, cls: Tensor, pos: Tensor) -> Tensor:
+    """h [B*(N+1), D] from the patch embeddings e [B*N, D]: the class token ``cls`` ([..., D])
+    prepended to every sample and the position embedding ``pos`` ([..., N+1, D]) added, both
+    read from the master parameters.  The backward sums their gradients over the batch in a
+    fixed order, straight into the flat gradient buffer when the parameters live in one."""
+    return _TokensAssembleFn.apply(e, cls, pos)
 
 
 class _GeluFn(Function):

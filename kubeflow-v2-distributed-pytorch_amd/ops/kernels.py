@@ -21,7 +21,7 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "stem_fwd_pool", "stem_bwd", "gemm", "cross_entropy_fwd_bwd", "cross_entropy_mixed_fwd_bwd",
            "batch_mix", "top1_correct", "eval_stats", "sgd_step",
            "adamw_step", "ema_update", "ema_swap", "ema_buffers_update", "ema_buffers_swap",
-           "layernorm_fwd", "layernorm_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
+           "layernorm_fwd", "layernorm_bwd", "patchify", "tokens_assemble_fwd", "tokens_assemble_bwd", "attention_fwd", "attention_bwd", "dropout_fwd", "colsum", "bn_bwd_collect", "stem_pack",
            "embedding_bwd", "gelu_fwd", "gelu_bwd", "nchw_to_nhwc", "record_decode", "record_decode_rrc",
            "record_augment", "batch_erase_",
            "use_native",
@@ -508,18 +508,27 @@ def layernorm_fwd(x, gamma, beta, eps, residual=None, drop=None):
     return _ref.layernorm_fwd(x, gamma, beta, eps, residual)
 
 
-def layernorm_bwd(dy, x, mean, rstd, gamma, acc=None, drop=None, dbias=None):
+def layernorm_bwd(dy, x, mean, rstd, gamma, acc=None, drop=None, dbias=None, dsum=None):
     """-> (dx, dgamma, dbeta, dxd); with ``acc=(dgamma_buf, dbeta_buf)`` the parameter grads are
     accumulated into those buffers and returned as None.  ``drop=(p, seed)``: dxd = dropout'(dx),
     the gradient of the dropped branch (else None).  ``dbias`` (fp32 [H]): also += Σ_rows of the
-    branch gradient (dxd, else dx) — the bias gradient of the Linear that produced x."""
+    branch gradient (dxd, else dx) — the bias gradient of the Linear that produced x.
+    ``dsum`` (like dx; not with ``drop``): the gradient of the residual stream that a pre-LN block
+    carries past this LayerNorm; dx = round(dx_ln + dsum), one rounding, and ``dbias`` sums that
+    total."""
+    dropping = drop is not None and drop[0] > 0.0
+    if dsum is not None and dropping:
+        raise ValueError("layernorm_bwd: dsum is not combined with the fused dropout")
     if use_native(dy):
         a = acc if acc is not None else (None, None)
-        if drop is not None and drop[0] > 0.0:
+        if dropping:
             sd, dev = _split_seed(drop[1])
             return native().layernorm_bwd(dy, x, mean, rstd, gamma, *a, drop[0], sd, dev, dbias)
+        if dsum is not None:
+            return native().layernorm_bwd(dy, x, mean, rstd, gamma, *a, dbias=dbias,
+                                          dsum=dsum.contiguous())
         return native().layernorm_bwd(dy, x, mean, rstd, gamma, *a, dbias=dbias)
-    dx, dg, db = _ref.layernorm_bwd(dy, x, mean, rstd, gamma)
+    dx, dg, db = _ref.layernorm_bwd(dy, x, mean, rstd, gamma, dsum)
     dxd = dropout_fwd(dx, drop[0], drop[1]) if drop is not None and drop[0] > 0.0 else None
     if dbias is not None:
         colsum((dxd if dxd is not None else dx).reshape(-1, dx.shape[-1]), dbias)
@@ -528,6 +537,38 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, acc=None, drop=None, dbias=None):
         acc[1].add_(db.to(acc[1].dtype))
         return dx, None, None, dxd
     return dx, dg, db, dxd
+
+
+def patchify(x, patch, dtype):
+    """x [B, C, H, W] (fp32 / bf16, NCHW contiguous) -> [B*(H/P)*(W/P), C*P*P] in ``dtype``: the
+    rows a P x P stride-P convolution multiplies with ``weight.view(D, C*P*P)``
+    (:func:`_ref.patchify` documents the order).  Native: P % 8 == 0, bf16 / fp32 output."""
+    if use_native(x):
+        return native().patchify(x.contiguous(), int(patch), dtype)
+    return _ref.patchify(x, patch, dtype)
+
+
+def tokens_assemble_fwd(e, cls, pos):
+    """e [B*N, D], cls [D], pos [(N+1)*D] -> h [B*(N+1), D]: the class token prepended and the
+    position embedding added (:func:`_ref.tokens_assemble_fwd`)."""
+    if use_native(e):
+        return native().tokens_assemble_fwd(e.contiguous(), cls, pos)
+    return _ref.tokens_assemble_fwd(e, cls, pos)
+
+
+def tokens_assemble_bwd(dh, batch, dpos_acc=None, dcls_acc=None):
+    """-> (de, dpos, dcls): de [B*N, D] = dh without the class rows (compact); dpos / dcls =
+    Σ_b dh[b] / Σ_b dh[b, 0], summed in ascending b by one owner per element (the same bits in
+    every run), accumulated into ``dpos_acc`` / ``dcls_acc`` (fp32, flat) and returned as None
+    when those are given."""
+    if use_native(dh):
+        return native().tokens_assemble_bwd(dh.contiguous(), int(batch), dpos_acc, dcls_acc)
+    de, dpos, dcls = _ref.tokens_assemble_bwd(dh, batch)
+    if dpos_acc is not None:
+        dpos_acc.add_(dpos.to(dpos_acc.dtype))
+        dcls_acc.add_(dcls.to(dcls_acc.dtype))
+        return de, None, None
+    return de, dpos, dcls
 
 
 def colsum(x, out=None):

@@ -24,7 +24,9 @@ Additions: ``--dtype``, ``--dataset``, ``--steps``, ``--bench``, ``--num_classes
 
 Large-batch training (``mipipe.optim.LARS`` / ``LAMB``; all of it stays on under ``--hip-graph``,
 the per-step values being device memory):
-  * ``--optimizer {sgd,lars,lamb}`` (default ``sgd``: the reference's SGD, unchanged);
+  * ``--optimizer {sgd,lars,lamb,adamw}`` (default ``sgd``: the reference's SGD, unchanged);
+    ``adamw`` is the flat-buffer ``mipipe.optim.AdamW`` at a constant ``--learning_rate`` with
+    ``--wd`` (the ViT recipe's optimizer; schedules, warm-up and clipping live in ``lamb``);
   * ``--lr-schedule {constant,linear,poly,cosine}`` with ``--lr-warmup-steps`` and
     ``--lr-total-steps`` (default ``num_epochs`` x steps per epoch): linear warm-up to
     ``--learning_rate``, then the decay to 0;
@@ -98,7 +100,7 @@ from mipipe.launch.env import device_offset, local_gpus
 from mipipe.parallel import DataParallel, DistributedDataParallel, DistributedSampler
 from mipipe.parallel import dist_utils
 from mipipe.data.synthetic import DATASET_SHAPES, DeviceBatchLoader, SyntheticImageDataset
-from mipipe.optim import SGD
+from mipipe.optim import SGD, AdamW
 from mipipe.ops import functional as MF
 from mipipe.ops import inference
 from mipipe.train import checkpoint as ckpt
@@ -116,6 +118,13 @@ def _make_optimizer(args, params, shadow_dtype):
     if args.optimizer == "sgd" and plain:
         return SGD(params, args.learning_rate, momentum=args.momentum,
                    weight_decay=args.weight_decay, shadow_dtype=shadow_dtype)
+    if args.optimizer == "adamw":
+        if not plain:
+            raise SystemExit("--optimizer adamw runs at a constant learning rate without "
+                             "clipping: for --lr-schedule / --lr-warmup-steps / --clip-grad-norm "
+                             "use --optimizer lamb, which keeps them on the device")
+        return AdamW(params, args.learning_rate, weight_decay=args.weight_decay,
+                     shadow_dtype=shadow_dtype)
     from mipipe.optim import LAMB, LARS, LRSchedule
     sched = LRSchedule(args.lr_schedule, args.learning_rate, args.lr_warmup_steps,
                        args.lr_total_steps or 0)
@@ -259,8 +268,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--momentum", default=0.9, type=float, metavar="M", help="momentum")
     p.add_argument("--wd", "--weight-decay", default=1e-4, type=float, metavar="W",
                    dest="weight_decay", help="weight decay (default: 1e-4)")
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars", "lamb"],
-                   help="sgd (default), lars (vision, large batch) or lamb (BERT, large batch)")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars", "lamb", "adamw"],
+                   help="sgd (default), lars (vision, large batch), lamb (transformers, large "
+                        "batch) or adamw (constant learning rate, --wd)")
     p.add_argument("--lr-schedule", default="constant",
                    choices=["constant", "linear", "poly", "cosine"],
                    help="learning-rate decay after the warm-up, evaluated on the device")
@@ -507,6 +517,12 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         kw["in_chans"] = C
     elif args.arch.startswith(("resnet", "wide_resnet", "resnext")):
         kw["in_chans"] = C
+    elif args.arch.startswith("vit_"):
+        # the position table is built for one image size (no interpolation)
+        if H != W:
+            raise SystemExit(f"--arch {args.arch} needs square images, got {H}x{W}")
+        kw["in_chans"] = C
+        kw["image_size"] = H
     model = create_model(args.arch, **kw)
     if args.pretrained:
         from mipipe.models import find_pretrained, load_pretrained
@@ -625,7 +641,8 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         train_loader = DeviceBatchLoader(train_set, args.batch_size, train_sampler, device)
         test_loader = DeviceBatchLoader(test_set, 128, test_sampler, device)
 
-    if not isinstance(optimizer, SGD) and args.lr_total_steps is None and start_epoch == 0:
+    if not isinstance(optimizer, (SGD, AdamW)) and args.lr_total_steps is None \
+            and start_epoch == 0:
         # the schedule ends with the run (its parameters are read from the group at every step)
         per_epoch = min(len(train_loader), args.steps) if args.steps else len(train_loader)
         optimizer.param_groups[0]["total_steps"] = args.num_epochs * per_epoch
