@@ -74,7 +74,11 @@ inline Tensor split_ws(long n, const Tensor& like) {
 inline float* wsp(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
 
 // torch's pooling output size (ceil_mode: the last window must start inside input or left pad)
+// A padded input shorter than the window has no output: C++ division truncates toward zero, so
+// a negative numerator would give extent 1 instead of torch's error.
 inline int pool_out(int L, int k, int s, int p, bool ceil_mode) {
+  TORCH_CHECK(L + 2 * p >= k, "padded input (", L, " + 2*", p, ") is smaller than the pooling window ",
+              k);
   int num = L + 2 * p - k;
   int o = (ceil_mode ? (num + s - 1) / s : num / s) + 1;
   if (ceil_mode && (o - 1) * s >= L + p) --o;

@@ -1014,9 +1014,18 @@ Tensor maxpool_bwd(Tensor dy, Tensor idx, std::vector<int64_t> xs, int k, int s,
   check_act(dy, "dy");
   check_cuda(idx, "idx");
   c10::DeviceGuard g(dy.device());
+  TORCH_CHECK(xs.size() == 4 && dy.dim() == 4, "maxpool_bwd: NHWC shapes expected");
   int N = xs[0], H = xs[1], W = xs[2], C = xs[3];
   int Ho = dy.size(1), Wo = dy.size(2);
-  TORCH_CHECK(idx.sizes() == dy.sizes() && dy.size(3) == C, "maxpool_bwd shape mismatch");
+  TORCH_CHECK(C % 8 == 0 && k <= 15, "maxpool needs C % 8 == 0 and k <= 15");
+  TORCH_CHECK(k >= 1 && s >= 1 && p >= 0 && 2 * p <= k, "bad maxpool geometry");
+  TORCH_CHECK(idx.scalar_type() == at::kByte && idx.sizes() == dy.sizes() && dy.size(3) == C,
+              "maxpool_bwd shape mismatch");
+  TORCH_CHECK(dy.size(0) == N, "maxpool_bwd: dy batch ", dy.size(0), " != x batch ", N);
+  // the forward's extent: floor, or ceil when it ran in ceil mode
+  TORCH_CHECK((Ho == pool_out(H, k, s, p, false) || Ho == pool_out(H, k, s, p, true)) &&
+                  (Wo == pool_out(W, k, s, p, false) || Wo == pool_out(W, k, s, p, true)),
+              "maxpool_bwd: dy extent ", Ho, " x ", Wo, " does not match the pooling geometry");
   auto dx = torch::empty({N, H, W, C}, dy.options());
   mipipe::maxpool_bwd(dy.data_ptr(), idx.data_ptr<uint8_t>(), dx.data_ptr(), N, H, W, C, Ho, Wo, k,
                       s, p, stream(), is_f32(dy));
@@ -1811,7 +1820,10 @@ mipipe::GConvShape gconv_shape(int64_t N, int64_t H, int64_t W, int64_t Ci, int6
   s.groups = (int)groups;
   TORCH_CHECK(s.KH >= 1 && s.KW >= 1 && s.sh >= 1 && s.sw >= 1 && s.ph >= 0 && s.pw >= 0,
               "bad kernel / stride / padding");
-  s.Ho = (s.H + 2 * s.ph - s.KH) / s.sh + 1;
+  // (checked before dividing: a negative numerator truncates toward zero and gives extent 1)
+  TORCH_CHECK(s.H + 2 * s.ph >= s.KH && s.W + 2 * s.pw >= s.KW, "padded input (", s.H + 2 * s.ph,
+              " x ", s.W + 2 * s.pw, ") is smaller than the kernel (", s.KH, " x ", s.KW, ")");
+  s.Ho =(s.H + 2 * s.ph - s.KH) / s.sh + 1;
   s.Wo = (s.W + 2 * s.pw - s.KW) / s.sw + 1;
   TORCH_CHECK(s.Ho > 0 && s.Wo > 0, "empty conv output");
   return s;
@@ -2064,6 +2076,14 @@ PYBIND11_MODULE(_C, m) {
         py::arg("residual") = py::none(), py::arg("relu") = false, py::arg("stride_w") = 0,
         py::arg("pad_w") = -1, py::arg("cfg") = -1);
   m.attr("STAT_REPLICAS") = mipipe::kStatReplicas;
+  // launch constants of vision.hip / pool.hip (launchers.hpp): the edge tests derive shapes from them
+  m.attr("V8_ROW_U") = mipipe::kV8RowU;
+  m.attr("V8_APPLY_U") = mipipe::kV8ApplyU;
+  m.attr("V8_REDUCE_BLOCKS") = mipipe::kV8ReduceBlocks;
+  m.attr("V8_APPLY_BLOCKS") = mipipe::kV8ApplyBlocks;
+  m.attr("CHAN_GRID_BLOCKS") = mipipe::kChanGridBlocks;
+  m.attr("GRID_FOR_BLOCKS") = mipipe::kGridForBlocks;
+  m.attr("EW_GRID_BLOCKS") = mipipe::kEwGridBlocks;
   m.def("conv_dgrad", &conv_dgrad, py::arg("dy"), py::arg("w"), py::arg("x_shape"),
         py::arg("stride"), py::arg("pad"), py::arg("addend") = py::none(),
         py::arg("bn_y") = py::none(), py::arg("bn_mean") = py::none(),

@@ -29,6 +29,19 @@ struct ConvShape {
 // every row) 10-35x slower — a net ResNet-50 loss of 30 % — so the layout stays at 16.
 constexpr int kStatReplicas = 16;
 extern int g_stat_rows;
+// Launch constants of vision.hip's any-C BatchNorm kernels and of the grid-stride elementwise /
+// gather kernels (vision.hip's grid_for, pool.hip's ew_grid).  They are exported to Python next to
+// STAT_REPLICAS so that the edge tests derive their shapes from the values the kernels use.
+// v8 ("C % 8 == 0, C <= 2048") BN kernels: the statistics / backward reductions keep kV8RowU rows
+// of loads in flight per thread over up to kV8ReduceBlocks blocks; the apply passes walk
+// contiguous tiles of kV8ApplyU rows per thread over up to kV8ApplyBlocks blocks.
+constexpr int kV8RowU = 4;
+constexpr int kV8ApplyU = 2;
+constexpr int kV8ReduceBlocks = 1024;
+constexpr int kV8ApplyBlocks = 4096;
+constexpr int kChanGridBlocks = 2048;  // generic-C BN reductions: blocks over (channel tile, rows)
+constexpr int kGridForBlocks = 8192;   // vision.hip grid_for: blocks of 256 threads
+constexpr int kEwGridBlocks = 4096;    // pool.hip ew_grid: blocks of 256 threads
 // Split-K sizing for the atomically-accumulated weight-gradient GEMMs: splits are chosen so
 // that tiles * splits ~= this many workgroups (tunable at runtime for sweeps).
 extern int g_splitk_target;

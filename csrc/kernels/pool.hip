@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_apply_kernel(
 
 static int ew_grid(long work) {
   long g = (work + 255) / 256;
-  return (int)std::max<long>(1, std::min<long>(g, 4096));
+  return (int)std::max<long>(1, std::min<long>(g, kEwGridBlocks));
 }
 
 void maxpool_fwd(const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, int Ho, int Wo,

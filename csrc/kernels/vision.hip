@@ -32,7 +32,7 @@ __device__ __forceinline__ bool act_pass(float z, int act) {
   return true;
 }
 
-static int grid_for(long work, int per_block = 256, int cap = 8192) {
+static int grid_for(long work, int per_block = 256, int cap = kGridForBlocks) {
   long g = (work + per_block - 1) / per_block;
   return (int)std::max<long>(1, std::min<long>(g, cap));
 }
@@ -576,12 +576,11 @@ __device__ __forceinline__ void lds_reduce_atomic8(float* sh, const float* v, in
 }
 
 // v8 ("any C % 8") BN kernels: the statistics / backward reductions keep kV8RowU rows of loads
-// in flight per thread over up to 1024 blocks whose per-channel atomics go to kStatReplicas
+// in flight per thread over up to kV8ReduceBlocks blocks whose per-channel atomics go to kStatReplicas
 // replica rows (one [C] row took every block's atomics: on DenseNet's concatenated inputs that
 // serialised the reductions at ~2 TB/s, and more blocks made it slower); the apply passes walk
-// contiguous tiles of kV8ApplyU rows per thread with the loads issued first (as bn.hip's)
-constexpr int kV8RowU = 4;
-constexpr int kV8ApplyU = 2;
+// contiguous tiles of kV8ApplyU rows per thread with the loads issued first (as bn.hip's).
+// kV8RowU, kV8ApplyU and the block caps are in launchers.hpp.
 
 template <class T>
 __global__ __launch_bounds__(256) void chan_stats_v8_kernel(const T* __restrict__ y,
@@ -773,7 +772,7 @@ static int v8_tiles(long M, int C, int U, int cap) {
 
 static dim3 chan_grid(long M, int C) {
   const int bx = (C + 63) / 64;
-  long by = std::max<long>(1, std::min<long>((M + 63) / 64, std::max(1, 2048 / bx)));
+  long by = std::max<long>(1, std::min<long>((M + 63) / 64, std::max(1, kChanGridBlocks / bx)));
   return dim3(bx, (unsigned)by);
 }
 
@@ -782,7 +781,7 @@ void chan_stats(const void* y, const float* shift, long M, int C, float* psum, f
   auto run = [&](auto tag) {
     typedef decltype(tag) T;
     if (bn_v8(C)) {
-      hipLaunchKernelGGL((chan_stats_v8_kernel<T>), dim3(v8_grid(M, C, 1024)), dim3(256), 0, st,
+      hipLaunchKernelGGL((chan_stats_v8_kernel<T>), dim3(v8_grid(M, C, kV8ReduceBlocks)), dim3(256), 0, st,
                          (const T*)y, shift, M, C, psum, psq);
       return;
     }
@@ -798,7 +797,7 @@ void affine_act(const void* y, const float* scale, const float* bias, void* z, l
   auto run = [&](auto tag) {
     typedef decltype(tag) T;
     if (bn_v8(C)) {
-      hipLaunchKernelGGL((affine_act_v8_kernel<T>), dim3(v8_tiles(M, C, kV8ApplyU, 4096)), dim3(256), 0, st,
+      hipLaunchKernelGGL((affine_act_v8_kernel<T>), dim3(v8_tiles(M, C, kV8ApplyU, kV8ApplyBlocks)), dim3(256), 0, st,
                          (const T*)y, scale, bias, (T*)z, M, C, act);
       return;
     }
@@ -816,7 +815,7 @@ void bn_generic_bwd_reduce(const void* dz, const void* z, const void* y, const f
   auto run = [&](auto tag) {
     typedef decltype(tag) T;
     if (bn_v8(C)) {
-      hipLaunchKernelGGL((bn_generic_bwd_reduce_v8_kernel<T>), dim3(v8_grid(M, C, 1024)), dim3(256), 0,
+      hipLaunchKernelGGL((bn_generic_bwd_reduce_v8_kernel<T>), dim3(v8_grid(M, C, kV8ReduceBlocks)), dim3(256), 0,
                          st, (const T*)dz, (const T*)z, (const T*)y, mean, invstd, M,
                          C, act, out_g, out_gx);
       return;
@@ -836,7 +835,7 @@ void bn_generic_bwd_apply(const void* dz, const void* z, const void* y, const fl
   auto run = [&](auto tag) {
     typedef decltype(tag) T;
     if (bn_v8(C)) {
-      hipLaunchKernelGGL((bn_generic_bwd_apply_v8_kernel<T>), dim3(v8_tiles(M, C, kV8ApplyU, 4096)), dim3(256), 0,
+      hipLaunchKernelGGL((bn_generic_bwd_apply_v8_kernel<T>), dim3(v8_tiles(M, C, kV8ApplyU, kV8ApplyBlocks)), dim3(256), 0,
                          st, (const T*)dz, (const T*)z, (const T*)y, mean, invstd,
                          gamma, sum_g, sum_gx, 1.f / (float)count, M, C, act, (T*)dy);
       return;

@@ -1,6 +1,7 @@
 """The argument checks the Python entries share (csrc/bind/common.hpp): ``ce_args`` for the five
 cross-entropy entries, ``top1_correct`` and ``eval_stats``; ``check_records`` for
-``record_decode``, ``record_decode_rrc`` and ``record_augment``.
+``record_decode``, ``record_decode_rrc`` and ``record_augment``; and the output-extent checks of
+the pools and the direct convolutions (``pool_out``, ``gconv_shape``, ``maxpool_bwd``).
 
 Every wrong call must raise ``RuntimeError`` with the shared checker's own message, on the host,
 before anything is launched (labels on another GPU, the one fault that three entries newly
@@ -211,3 +212,102 @@ def test_record_entries_accept(nat):
     assert torch.equal(x, rx) and torch.equal(y, ry)
     out = REC_ENTRIES["record_augment"](nat, rec, idx, affine, LB)
     assert torch.equal(out, _ref.record_augment(rec, idx, (C, H, W), 3, 2, LB))
+
+
+# ------------------------------------------------------------- pooling / direct-conv geometry
+# pool_out (csrc/bind/common.hpp) and gconv_shape (csrc/bindings.cpp): a padded input smaller than
+# the window has no output.  H = 2, k = 3, s = 2, p = 0 once gave extent 1 (C++ division truncates
+# -1 / 2 to 0) and a kernel launch over a partial window; torch raises.  H = 3 is the smallest
+# valid input: a 1x1 output.  C = 8 depthwise, so dy is [1, 1, 1, 8] in both cases.
+GC = 8
+GEO_MESSAGE = "is smaller than the"
+
+
+def _geo_x(H):
+    g = torch.Generator().manual_seed(3)
+    return torch.randint(-3, 4, (1, H, H, GC), generator=g).to(torch.bfloat16).cuda()
+
+
+def _geo_w():
+    g = torch.Generator().manual_seed(4)
+    return (torch.randint(0, 2, (GC, 3, 3, 1), generator=g) * 2 - 1).to(torch.bfloat16).cuda()
+
+
+def _geo_dy():
+    return torch.tensor([1, -2, 3, -1, 2, -3, 1, 2]).reshape(1, 1, 1, GC).to(torch.bfloat16).cuda()
+
+
+GEO_ENTRIES = {
+    "maxpool_fwd": lambda c, H: c.maxpool_fwd(_geo_x(H), 3, 2, 0, False)[0],
+    "avgpool2d_fwd": lambda c, H: c.avgpool2d_fwd(_geo_x(H), 3, 2, 0),
+    "gconv_fwd": lambda c, H: c.gconv_fwd(_geo_x(H), _geo_w(), [2, 2], [0, 0], GC, None, 0),
+    "gconv_dgrad": lambda c, H: c.gconv_dgrad(_geo_dy(), _geo_w(), [1, H, H, GC], [2, 2], [0, 0],
+                                              GC, None, 0),
+    "gconv_wgrad": lambda c, H: c.gconv_wgrad(_geo_dy(), _geo_x(H), 3, 3, [2, 2], [0, 0], GC, None,
+                                              0, None, None, True)[0],
+}
+
+
+@pytest.mark.parametrize("entry", list(GEO_ENTRIES))
+def test_window_larger_than_input_rejects(nat, entry):
+    with pytest.raises(RuntimeError, match=GEO_MESSAGE):
+        GEO_ENTRIES[entry](nat, 2)
+
+
+def test_window_equal_to_input_accepts(nat):
+    x, w, dy = _geo_x(3), _geo_w(), _geo_dy()
+    xn = x.float().permute(0, 3, 1, 2)
+    y = GEO_ENTRIES["maxpool_fwd"](nat, 3)
+    assert y.shape == (1, 1, 1, GC)
+    assert torch.equal(y.float(), torch.nn.functional.max_pool2d(xn, 3, 2, 0).permute(0, 2, 3, 1))
+    y = GEO_ENTRIES["avgpool2d_fwd"](nat, 3)
+    ref = torch.nn.functional.avg_pool2d(xn.double(), 3, 2, 0).permute(0, 2, 3, 1)
+    assert y.shape == (1, 1, 1, GC)
+    # one bf16 rounding of sum / 9: half an ulp, 2^-9 relative
+    assert bool(((y.double() - ref).abs() <= ref.abs() * 2.0 ** -8).all())
+    # integer data: the 27-term sums are exact in bf16, so the conv results equal torch's
+    y = GEO_ENTRIES["gconv_fwd"](nat, 3)
+    assert y.shape == (1, 1, 1, GC)
+    assert torch.equal(y.float(), _ref.gconv_fwd(x.float(), w.float(), (2, 2), (0, 0), GC))
+    dx = GEO_ENTRIES["gconv_dgrad"](nat, 3)
+    assert torch.equal(dx.float(), _ref.gconv_dgrad(dy.float(), w.float(), (1, 3, 3, GC), (2, 2),
+                                                    (0, 0), GC))
+    dw = GEO_ENTRIES["gconv_wgrad"](nat, 3)
+    assert torch.equal(dw, _ref.gconv_wgrad(dy.float(), x.float(), 3, 3, (2, 2), (0, 0), GC)[0])
+
+
+def _pool_bwd_args(C=8):
+    """A valid maxpool_bwd call: x [2, 7, 7, C], 3/2/1 -> 4x4 (floor and ceil extents agree)."""
+    dy = torch.ones(2, 4, 4, C, dtype=torch.bfloat16, device="cuda")
+    idx = torch.full((2, 4, 4, C), 4, dtype=torch.uint8, device="cuda")   # the window's centre
+    return dy, idx, [2, 7, 7, C]
+
+
+@pytest.mark.parametrize("case", ["batch", "extent", "channels"])
+def test_maxpool_bwd_rejects(nat, case):
+    dy, idx, xs = _pool_bwd_args(12 if case == "channels" else 8)
+    if case == "batch":
+        xs[0] = 3
+        msg = "dy batch"
+    elif case == "extent":      # 5x5 is neither the floor nor the ceil extent of 7 / 3 / 2 / 1
+        dy = torch.ones(2, 5, 5, 8, dtype=torch.bfloat16, device="cuda")
+        idx = torch.zeros(2, 5, 5, 8, dtype=torch.uint8, device="cuda")
+        msg = "does not match the pooling geometry"
+    else:
+        msg = "C % 8 == 0"
+    with pytest.raises(RuntimeError, match=msg):
+        nat.maxpool_bwd_impl(dy, idx, xs, 3, 2, 1)
+
+
+def test_maxpool_bwd_accepts(nat):
+    dy, idx, xs = _pool_bwd_args()
+    dx = nat.maxpool_bwd_impl(dy, idx, xs, 3, 2, 1)
+    want = torch.zeros(xs)
+    want[:, 0::2, 0::2, :] = 1.0      # centre of window (ho, wo) is pixel (2 ho, 2 wo)
+    assert torch.equal(dx.float().cpu(), want)
+    # a ceil-mode extent (8 / 3 / 2 / 0: floor 3, ceil 4) is accepted as well
+    x = torch.arange(2 * 8 * 8 * 8, dtype=torch.float32).reshape(2, 8, 8, 8).to(torch.bfloat16).cuda()
+    y, idx = nat.maxpool_fwd(x, 3, 2, 0, True)
+    assert y.shape == (2, 4, 4, 8)
+    dx = nat.maxpool_bwd_impl(torch.ones_like(y), idx, [2, 8, 8, 8], 3, 2, 0)
+    assert dx.float().sum().item() == y.numel()
