@@ -680,6 +680,7 @@ Tensor bn_act_fwd(Tensor y, Tensor scale, Tensor bias, bool relu, optional<Tenso
                   optional<Tensor> rscale, optional<Tensor> rbias, optional<Tensor> mask) {
   check_act(y, "y");
   c10::DeviceGuard g(y.device());
+  TORCH_CHECK(y.numel() > 0, "bn_act_fwd: empty input");
   int64_t C = y.size(-1), M = y.numel() / C;
   TORCH_CHECK(C % 8 == 0, "bn_act_fwd needs C % 8 == 0");
   check_vec(scale, C, "scale");
@@ -716,6 +717,7 @@ std::tuple<Tensor, Tensor, optional<Tensor>> bn_act_bwd_reduce(
   check_same(dz, y, "dz");
   check_same(z, y, "z");
   c10::DeviceGuard g(dz.device());
+  TORCH_CHECK(y.numel() > 0, "bn_act_bwd_reduce: empty input");
   int64_t C = y.size(-1), M = y.numel() / C;
   TORCH_CHECK(C % 8 == 0 && dz.sizes() == y.sizes() && z.sizes() == y.sizes(), "shape mismatch");
   check_vec(mean, C, "mean");
@@ -762,6 +764,7 @@ std::tuple<Tensor, optional<Tensor>> bn_act_bwd_apply(
   check_same(dz, y, "dz");
   check_same(z, y, "z");
   c10::DeviceGuard g(dz.device());
+  TORCH_CHECK(y.numel() > 0, "bn_act_bwd_apply: empty input");
   int64_t C = y.size(-1), M = y.numel() / C;
   TORCH_CHECK(C % 8 == 0 && dz.sizes() == y.sizes() && z.sizes() == y.sizes(), "shape mismatch");
   for (auto* t : {&mean, &invstd, &gamma, &sum_g, &sum_gx}) check_vec(*t, C, "bn vector");
@@ -2084,6 +2087,20 @@ PYBIND11_MODULE(_C, m) {
   m.attr("CHAN_GRID_BLOCKS") = mipipe::kChanGridBlocks;
   m.attr("GRID_FOR_BLOCKS") = mipipe::kGridForBlocks;
   m.attr("EW_GRID_BLOCKS") = mipipe::kEwGridBlocks;
+  // launch constants of bn.hip, and the grid / unroll actually in effect
+  m.attr("BN_THREADS") = mipipe::kBnThreads;
+  m.attr("BN_ROW_U") = mipipe::kBnRowU;
+  m.attr("BN_APPLY_U") = mipipe::kBnApplyU;
+  m.attr("BN_REDUCE_BLOCKS") = mipipe::kBnReduceBlocks;
+  m.attr("BN_ATOMIC_BUDGET") = (int64_t)mipipe::kBnAtomicBudget;
+  m.attr("BN_MIN_BLOCKS") = mipipe::kBnMinBlocks;
+  m.attr("BN_ROW_ITERS") = mipipe::kBnRowIters;
+  m.attr("DET_CHUNK_ROWS") = mipipe::kDetChunkRows;
+  m.def("bn_bwd_reduce_blocks", [](int64_t M, int64_t C) {
+    TORCH_CHECK(M >= 0 && C >= 8 && C % 8 == 0, "bn_bwd_reduce_blocks: M >= 0, C % 8 == 0");
+    return mipipe::bn_bwd_reduce_blocks((long)M, (int)C);
+  });
+  m.def("bn_apply_u", []() { return mipipe::bn_apply_u(); });
   m.def("conv_dgrad", &conv_dgrad, py::arg("dy"), py::arg("w"), py::arg("x_shape"),
         py::arg("stride"), py::arg("pad"), py::arg("addend") = py::none(),
         py::arg("bn_y") = py::none(), py::arg("bn_mean") = py::none(),

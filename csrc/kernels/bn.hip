@@ -16,8 +16,9 @@ namespace mipipe {
 
 namespace {
 
-constexpr int kT = 256;
-constexpr int kRowU = 4;  // rows per thread-iteration of bn_bwd_reduce (loads in flight)
+// launch constants: launchers.hpp (exported to Python for the edge tests)
+constexpr int kT = kBnThreads;
+constexpr int kRowU = kBnRowU;  // rows per thread-iteration of bn_bwd_reduce (loads in flight)
 
 struct RowMap {
   int tpr;   // threads per row (C/8), capped at 256 per pass
@@ -230,10 +231,10 @@ void bn_fold_affine(const float* gamma, const float* beta, const float* mean, co
 // kApplyU rows before any arithmetic (two 16-B loads per stream in flight instead of one).
 // tools/r2/bnlab.hip at ResNet-50 b256 shapes: 5.3 -> 5.7-6.1 TB/s vs the grid-stride loop with
 // one row in flight (4-8 rows per thread measured no better, grid-strided rows worse).
-constexpr int kApplyU = 2;
+constexpr int kApplyU = kBnApplyU;
 
 template <int RES, class T, int U = kApplyU>  // RES: 0 none, 1 raw residual, 2 BN'd residual
-__global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y,
+__global__ __launch_bounds__(kT) void bn_act_fwd_kernel(const T* __restrict__ y,
                                                          const float* __restrict__ scale,
                                                          const float* __restrict__ bias,
                                                          const T* __restrict__ r,
@@ -306,10 +307,11 @@ inline int grid_for_tiles(long M, int rpb, int u = kApplyU) {
 static int bn_u() {
   static const int u = [] {
     const char* v = getenv("MIPIPE_BN_U");
-    return v != nullptr && atoi(v) == 4 ? 4 : 2;
+    return v != nullptr && atoi(v) == 4 ? 4 : kApplyU;
   }();
   return u;
 }
+int bn_apply_u() { return bn_u(); }
 
 template <class T>
 static void bn_act_fwd_t(const void* y, const float* scale, const float* bias, const void* r,
@@ -325,18 +327,18 @@ static void bn_act_fwd_t(const void* y, const float* scale, const float* bias, c
   T* zp = (T*)z;
   if (r == nullptr)
     {
-      if (u == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<0, T, 4>), dim3(grid), dim3(256), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
-      else hipLaunchKernelGGL((bn_act_fwd_kernel<0, T>), dim3(grid), dim3(256), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
+      if (u == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<0, T, 4>), dim3(grid), dim3(kT), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
+      else hipLaunchKernelGGL((bn_act_fwd_kernel<0, T>), dim3(grid), dim3(kT), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
     }
   else if (rscale == nullptr)
     {
-      if (u == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<1, T, 4>), dim3(grid), dim3(256), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
-      else hipLaunchKernelGGL((bn_act_fwd_kernel<1, T>), dim3(grid), dim3(256), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
+      if (u == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<1, T, 4>), dim3(grid), dim3(kT), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
+      else hipLaunchKernelGGL((bn_act_fwd_kernel<1, T>), dim3(grid), dim3(kT), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
     }
   else
     {
-      if (u == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<2, T, 4>), dim3(grid), dim3(256), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
-      else hipLaunchKernelGGL((bn_act_fwd_kernel<2, T>), dim3(grid), dim3(256), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
+      if (u == 4) hipLaunchKernelGGL((bn_act_fwd_kernel<2, T, 4>), dim3(grid), dim3(kT), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
+      else hipLaunchKernelGGL((bn_act_fwd_kernel<2, T>), dim3(grid), dim3(kT), 0, st, yp, scale, bias, rp, rscale, rbias, zp, M, C, relu, mask, nt, ntl);
     }
 }
 
@@ -349,7 +351,7 @@ void bn_act_fwd(const void* y, const float* scale, const float* bias, const void
 
 // ----------------------------------------------------------------------------- backward
 template <bool TWO, class T>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
+__global__ __launch_bounds__(kT) void bn_bwd_reduce_kernel(
     const T* __restrict__ dz, const T* __restrict__ z, const T* __restrict__ y,
     const float* __restrict__ mean, const float* __restrict__ invstd,
     const T* __restrict__ y2, const float* __restrict__ mean2,
@@ -564,10 +566,11 @@ void bn_bwd_collect_rows(float* rows, int P, int C, bool two, float* out_g, floa
 
 int bn_bwd_reduce_blocks(long M, int C) {
   RowMap mp = row_map(C);
-  // >= 16 row-iterations per thread, and at most ~1M atomic adds in total
-  long cap = std::max<long>(64, (1l << 20) / (3l * C));
-  return (int)std::max<long>(1, std::min<long>(std::min<long>(1024, cap),
-                                               (M + mp.rpb * 16 - 1) / (mp.rpb * 16)));
+  // >= kBnRowIters row-iterations per thread, and at most ~1M atomic adds in total
+  long cap = std::max<long>(kBnMinBlocks, kBnAtomicBudget / (3l * C));
+  const long rows = (long)mp.rpb * kBnRowIters;
+  return (int)std::max<long>(1, std::min<long>(std::min<long>(kBnReduceBlocks, cap),
+                                               (M + rows - 1) / rows));
 }
 
 void bn_act_bwd_reduce(const void* dz, const void* z, const void* y, const float* mean,
@@ -583,9 +586,9 @@ void bn_act_bwd_reduce(const void* dz, const void* z, const void* y, const float
     typedef decltype(tag) T;
       const T *dzp = (const T*)dz, *zp = (const T*)z, *yp = (const T*)y, *y2p = (const T*)y2;
     if (y2 == nullptr)
-      hipLaunchKernelGGL((bn_bwd_reduce_kernel<false, T>), dim3(G), dim3(256), 0, st, dzp, zp, yp, mean, invstd, y2p, mean2, invstd2, relu, M, C, part, det_rows);
+      hipLaunchKernelGGL((bn_bwd_reduce_kernel<false, T>), dim3(G), dim3(kT), 0, st, dzp, zp, yp, mean, invstd, y2p, mean2, invstd2, relu, M, C, part, det_rows);
     else
-      hipLaunchKernelGGL((bn_bwd_reduce_kernel<true, T>), dim3(G), dim3(256), 0, st, dzp, zp, yp, mean, invstd, y2p, mean2, invstd2, relu, M, C, part, det_rows);
+      hipLaunchKernelGGL((bn_bwd_reduce_kernel<true, T>), dim3(G), dim3(kT), 0, st, dzp, zp, yp, mean, invstd, y2p, mean2, invstd2, relu, M, C, part, det_rows);
   };
   if (f32) launch(float{});
   else launch(__bf16{});
@@ -602,7 +605,7 @@ void bn_act_bwd_reduce(const void* dz, const void* z, const void* y, const float
 }
 
 template <int MODE, class T, int U = kApplyU>  // MODE 0: dy only, 1: dy + dres (=g), 2: dy + dy2 (second branch)
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
+__global__ __launch_bounds__(kT) void bn_bwd_apply_kernel(
     const T* __restrict__ dz, const T* __restrict__ z, const T* __restrict__ y,
     const float* __restrict__ mean, const float* __restrict__ invstd,
     const float* __restrict__ gamma, const float* __restrict__ sum_g,
@@ -693,18 +696,18 @@ void bn_act_bwd_apply(const void* dz, const void* z, const void* y, const float*
     T *dyp = (T*)dy, *dop = (T*)dother;
     if (y2 != nullptr)
       {
-        if (u == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<2, T, 4>), dim3(grid), dim3(256), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
-        else hipLaunchKernelGGL((bn_bwd_apply_kernel<2, T>), dim3(grid), dim3(256), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
+        if (u == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<2, T, 4>), dim3(grid), dim3(kT), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
+        else hipLaunchKernelGGL((bn_bwd_apply_kernel<2, T>), dim3(grid), dim3(kT), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
       }
     else if (want_dres)
       {
-        if (u == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<1, T, 4>), dim3(grid), dim3(256), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
-        else hipLaunchKernelGGL((bn_bwd_apply_kernel<1, T>), dim3(grid), dim3(256), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
+        if (u == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<1, T, 4>), dim3(grid), dim3(kT), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
+        else hipLaunchKernelGGL((bn_bwd_apply_kernel<1, T>), dim3(grid), dim3(kT), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
       }
     else
       {
-        if (u == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<0, T, 4>), dim3(grid), dim3(256), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
-        else hipLaunchKernelGGL((bn_bwd_apply_kernel<0, T>), dim3(grid), dim3(256), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
+        if (u == 4) hipLaunchKernelGGL((bn_bwd_apply_kernel<0, T, 4>), dim3(grid), dim3(kT), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
+        else hipLaunchKernelGGL((bn_bwd_apply_kernel<0, T>), dim3(grid), dim3(kT), 0, st, dzp, zp, yp, mean, invstd, gamma, sum_g, sum_gx, y2p, mean2, invstd2, gamma2, sum_gx2, inv_n, relu, dyp, dop, M, C, nt, ntl);
       }
   };
   if (f32) launch(float{});

@@ -42,6 +42,20 @@ constexpr int kV8ApplyBlocks = 4096;
 constexpr int kChanGridBlocks = 2048;  // generic-C BN reductions: blocks over (channel tile, rows)
 constexpr int kGridForBlocks = 8192;   // vision.hip grid_for: blocks of 256 threads
 constexpr int kEwGridBlocks = 4096;    // pool.hip ew_grid: blocks of 256 threads
+// bn.hip (training BatchNorm, C % 8 == 0): blocks of kBnThreads threads, a thread owns one
+// 8-channel group and rows; tpr = C/8 threads per row (capped at kBnThreads, then several
+// channel passes), rpb = kBnThreads / tpr rows per block pass.  The reduction keeps kBnRowU rows
+// of loads in flight per thread; the apply passes walk tiles of rpb * U rows per block, U =
+// kBnApplyU (or 4: bn_apply_u()).  bn_bwd_reduce_blocks: >= kBnRowIters row-iterations per
+// thread, at most kBnReduceBlocks blocks and about kBnAtomicBudget atomic adds (3 per channel
+// and block), but never fewer than kBnMinBlocks blocks for a long M.
+constexpr int kBnThreads = 256;
+constexpr int kBnRowU = 4;
+constexpr int kBnApplyU = 2;
+constexpr int kBnReduceBlocks = 1024;
+constexpr long kBnAtomicBudget = 1l << 20;
+constexpr int kBnMinBlocks = 64;
+constexpr int kBnRowIters = 16;
 // Split-K sizing for the atomically-accumulated weight-gradient GEMMs: splits are chosen so
 // that tiles * splits ~= this many workgroups (tunable at runtime for sweeps).
 extern int g_splitk_target;
@@ -319,6 +333,8 @@ void bn_act_bwd_reduce(const void* dz, const void* z, const void* y, const float
 // output, mean = β and invstd = null this turns Σg·(z-β) into Σg·x̂, x̂ = (z-β)/γ where z > 0.)
 // grid size of the reduce pass: deterministic mode needs det_ws = [3][blocks][C] floats
 int bn_bwd_reduce_blocks(long M, int C);
+// rows in flight per thread of the two apply passes (kBnApplyU, or 4 with MIPIPE_BN_U=4)
+int bn_apply_u();
 // Sum the replica rows of a bwd slab (filled by a fused dgrad epilogue) into out_g / out_gx,
 // re-zero it, optionally accumulate dγ += Σg·x̂, dβ += Σg.
 void bn_bwd_collect(float* rep, int C, float* out_g, float* out_gx, float* dgamma, float* dbeta,

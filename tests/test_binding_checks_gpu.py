@@ -311,3 +311,45 @@ def test_maxpool_bwd_accepts(nat):
     assert y.shape == (2, 4, 4, 8)
     dx = nat.maxpool_bwd_impl(torch.ones_like(y), idx, [2, 8, 8, 8], 3, 2, 0)
     assert dx.float().sum().item() == y.numel()
+
+
+# --------------------------------------------------------------------------- BatchNorm, empty input
+# bn.hip's apply kernels clamp their row to M - 1 and load before the bounds check, so M = 0 must
+# be refused on the host: [0, 8] (no rows) and [4, 0] (no channels), bf16 and fp32.
+def _bn_vec(C):
+    return torch.ones(C, dtype=torch.float32, device="cuda")
+
+
+def _bn_empty(shape, dtype):
+    return torch.zeros(shape, dtype=dtype, device="cuda")
+
+
+BN_EMPTY_ENTRIES = {
+    "bn_act_fwd": lambda c, t, C: c.bn_act_fwd(t, _bn_vec(C), _bn_vec(C), True, None, None, None),
+    "bn_act_fwd_residual": lambda c, t, C: c.bn_act_fwd(t, _bn_vec(C), _bn_vec(C), True, t, None,
+                                                        None),
+    "bn_act_bwd_reduce": lambda c, t, C: c.bn_act_bwd_reduce(t, t, t, _bn_vec(C), _bn_vec(C), True),
+    "bn_act_bwd_apply": lambda c, t, C: c.bn_act_bwd_apply(
+        t, t, t, _bn_vec(C), _bn_vec(C), _bn_vec(C), _bn_vec(C), _bn_vec(C), 16, True, True, None,
+        None, None, None, None),
+}
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("shape", [(0, 8), (4, 0)], ids=["no_rows", "no_channels"])
+@pytest.mark.parametrize("entry", list(BN_EMPTY_ENTRIES))
+def test_bn_entries_reject_empty(nat, entry, shape, dtype):
+    with pytest.raises(RuntimeError, match="empty input"):
+        BN_EMPTY_ENTRIES[entry](nat, _bn_empty(shape, dtype), shape[1])
+
+
+def test_bn_entries_accept_one_row(nat):
+    """The smallest valid input, [1, 8] of ones with unit vectors: z = 2, the sums are 1 and 0."""
+    t = torch.ones(1, 8, dtype=torch.bfloat16, device="cuda")
+    z = BN_EMPTY_ENTRIES["bn_act_fwd"](nat, t, 8)
+    assert z.shape == (1, 8) and bool((z == 2).all())
+    sg, sgx, sgx2 = BN_EMPTY_ENTRIES["bn_act_bwd_reduce"](nat, t, 8)
+    assert sg.tolist() == [1.0] * 8 and sgx.tolist() == [0.0] * 8 and sgx2 is None
+    dy, dres = BN_EMPTY_ENTRIES["bn_act_bwd_apply"](nat, t, 8)
+    # dy = 1 * (g - 1/16 - 0 * 1/16) with g = 1
+    assert dy.float().tolist() == [[0.9375] * 8] and bool((dres == 1).all())
