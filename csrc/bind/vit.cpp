@@ -15,7 +15,8 @@ Tensor patchify(Tensor x, int64_t P, at::ScalarType dt) {
   check_act(x, "x");
   TORCH_CHECK(x.dim() == 4, "x must be [B, C, H, W], got ", x.dim(), " dimensions");
   const int64_t B = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  TORCH_CHECK(P >= 8 && P % 8 == 0, "patch size must be a positive multiple of 8, got ", P);
+  TORCH_CHECK(P == 4 || (P >= 8 && P % 8 == 0),
+              "patch size must be 4 or a positive multiple of 8, got ", P);
   TORCH_CHECK(C >= 1, "x must have at least one channel");
   TORCH_CHECK(H >= P && W >= P && H % P == 0 && W % P == 0, "image ", H, "x", W,
               " is not a whole number of ", P, "x", P, " patches");

@@ -2054,6 +2054,7 @@ namespace mipipe_bind {
 void bind_loss(py::module& m);  // csrc/bind/loss.cpp: cross-entropy, top-1, evaluation statistics
 void bind_data(py::module& m);  // csrc/bind/data.cpp: layout, synthetic data, records, batch mix
 void bind_vit(py::module& m);   // csrc/bind/vit.cpp: patchify, token assembly
+void bind_convnext(py::module& m);  // csrc/bind/convnext.cpp: dwconv7, scale_residual
 }
 
 namespace mipipe_comm {
@@ -2068,6 +2069,7 @@ PYBIND11_MODULE(_C, m) {
   mipipe_bind::bind_loss(m);
   mipipe_bind::bind_data(m);
   mipipe_bind::bind_vit(m);
+  mipipe_bind::bind_convnext(m);
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
         py::arg("shift") = py::none(), py::arg("slab_sum") = py::none(),
         py::arg("slab_sq") = py::none(), py::arg("bias") = py::none(), py::arg("relu") = false,

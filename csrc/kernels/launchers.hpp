@@ -395,7 +395,8 @@ void cross_entropy_bwd(const void* logits, const int64_t* labels, const float* m
 void batch_mix(const void* x, void* out, const float* mix, int B, int C, int H, int W, bool f32,
                hipStream_t st);
 // Vision Transformer input side (vit.hip).  patchify: x [B, C, H, W] -> out [B*(H/P)*(W/P), C*P*P],
-// column (c, u, v) = conv_proj.weight.view(D, -1)'s; H % P == W % P == P % 8 == 0, 16-byte aligned.
+// column (c, u, v) = conv_proj.weight.view(D, -1)'s; H % P == W % P == 0, P % 8 == 0 or P == 4,
+// 16-byte aligned.
 void patchify(const void* x, void* out, int B, int C, int H, int W, int P, bool in_f32,
               bool out_f32, hipStream_t st);
 // h [B*(N+1), D]: row (b, 0) = cls + pos[0], row (b, 1 + n) = e[b*N + n] + pos[1 + n]; D % 8 == 0

@@ -3,6 +3,7 @@
 // scatter, column sums, dropout and the stem packing.  16-B vector accesses throughout
 // (cdna_hip_programming.md Guideline 13).  The loss lives in loss.hip, the optimizers in optim.hip.
 #include "common.hpp"
+#include "drop_hash.hpp"
 #include "launchers.hpp"
 
 namespace mipipe {
@@ -682,26 +683,9 @@ void embedding_bwd_sorted(const void* dy, const int64_t* sorted_ids, const int64
 }
 
 // ------------------------------------------------------------------------------ dropout hash
-// keep(element i) = hash(seed, i) >= p * 2^32; the per-step part of a device seed (graph replay)
-// is mixed in from seed_dev.  Shared by the standalone dropout kernel and the LayerNorm kernels
-// that fuse the residual branch's dropout (identical masks: same element index, same hash).
-__device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
-  x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-  return x;
-}
-
-__device__ __forceinline__ uint32_t drop_base(uint32_t seed, const uint32_t* seed_dev) {
-  if (seed_dev != nullptr) {  // L2-served agent-scope load (see attention.hip eff_seed)
-    const uint32_t c = __hip_atomic_load(seed_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    seed = drop_mix(seed ^ (c * 0x9e3779b1u + 0x632be5abu));
-  }
-  return drop_mix(seed * 0x9e3779b1u + 0x7f4a7c15u);
-}
-
-__device__ __forceinline__ bool drop_keep(uint32_t base, long idx, uint32_t thr) {
-  return drop_mix(base ^ (uint32_t)idx * 0x85ebca77u) >= thr;
-}
-
+// drop_mix / drop_base / drop_keep: drop_hash.hpp.  Shared by the standalone dropout kernel and
+// the LayerNorm kernels that fuse the residual branch's dropout (identical masks: same element
+// index, same hash).
 struct DropArgs {  // by value into the kernels; thr == 0 and scale == 1 when p == 0
   float scale;
   uint32_t thr, seed;

@@ -76,6 +76,48 @@ __global__ __launch_bounds__(kVitThreads) void patchify_kernel(const TI* __restr
   }
 }
 
+// P == 4 (ConvNeXt's stem): 8 output columns are two 4-pixel patch rows (c, u, 0..3), (c, u + 1,
+// 0..3) with u even, i.e. two 4-element source runs one image row apart: 8-byte (bf16) / 16-byte
+// (fp32) loads, one 16-byte store per 8 bf16.
+__device__ __forceinline__ void ld4(const __bf16* p, float* f) {
+  unpack4(*reinterpret_cast<const uint2*>(p), f);
+}
+__device__ __forceinline__ void ld4(const float* p, float* f) {
+  const float4 a = *reinterpret_cast<const float4*>(p);
+  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
+}
+
+template <class TI, class TO>
+__global__ __launch_bounds__(kVitThreads) void patchify4_kernel(const TI* __restrict__ x,
+                                                                TO* __restrict__ out,
+                                                                uint32_t items, FastDiv fC2,
+                                                                FastDiv fgw, FastDiv fgh, int C,
+                                                                int H, int W) {
+  constexpr uint32_t kTile = kVitThreads * kItems;
+  for (uint32_t t0 = blockIdx.x * kTile; t0 < items; t0 += gridDim.x * kTile) {
+    float f[kItems][8];
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {  // the tail's lanes re-read the last item (valid memory)
+      const uint32_t o = min(t0 + threadIdx.x + k * kVitThreads, items - 1);
+      const uint32_t r = fC2.div(o);  // output row (b, i, j)
+      const uint32_t cu = o - r * fC2.d;
+      const uint32_t c = cu >> 1, u = (cu & 1) * 2;
+      const uint32_t t = fgw.div(r);
+      const uint32_t j = r - t * fgw.d;
+      const uint32_t b = fgh.div(t);
+      const uint32_t i = t - b * fgh.d;
+      const long src = ((((long)b * C + c) * H + i * 4 + u) * W) + (long)j * 4;
+      ld4(x + src, f[k]);
+      ld4(x + src + W, f[k] + 4);
+    }
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+      const uint32_t o = t0 + threadIdx.x + k * kVitThreads;
+      if (o < items) store8(out + (long)o * 8, f[k]);
+    }
+  }
+}
+
 // --------------------------------------------------------------------- tokens_assemble_fwd
 template <class T>
 __global__ __launch_bounds__(kVitThreads) void tokens_fwd_kernel(
@@ -188,6 +230,18 @@ void patchify(const void* x, void* out, int B, int C, int H, int W, int P, bool 
   const long n = (long)B * C * H * W;
   if (n <= 0) return;
   const uint32_t items = (uint32_t)(n / 8);
+  if (P == 4) {
+    const FastDiv fC2((uint32_t)C * 2), fgw((uint32_t)(W / 4)), fgh((uint32_t)(H / 4));
+    dispatch_act(in_f32, [&](auto ti) {
+      dispatch_act(out_f32, [&](auto to) {
+        using TI = decltype(ti);
+        using TO = decltype(to);
+        hipLaunchKernelGGL((patchify4_kernel<TI, TO>), dim3(vit_grid(items)), dim3(kVitThreads),
+                           0, st, (const TI*)x, (TO*)out, items, fC2, fgw, fgh, C, H, W);
+      });
+    });
+    return;
+  }
   PatchGeom g;
   g.fP8 = FastDiv((uint32_t)P / 8);
   g.fP = FastDiv((uint32_t)P);

@@ -27,13 +27,14 @@ def register_model(name: str, fn: Callable) -> None:
     _REGISTRY[name] = fn
 
 
-_ZOO_MODULES = ("vgg", "mobilenet", "shufflenet", "squeezenet", "densenet", "inception", "bert", "vit")
+_ZOO_MODULES = ("vgg", "mobilenet", "shufflenet", "squeezenet", "densenet", "inception", "bert", "vit",
+                "convnext")
 
 
 def _lazy_register():
     """Import the remaining families (torchvision's registry: VGG/AlexNet, MobileNetV2, MNASNet,
-    ShuffleNetV2, SqueezeNet, DenseNet, GoogLeNet, Inception-v3, the Vision Transformers; plus
-    BERT)."""
+    ShuffleNetV2, SqueezeNet, DenseNet, GoogLeNet, Inception-v3, the Vision Transformers,
+    ConvNeXt; plus BERT)."""
     import importlib
     for name in _ZOO_MODULES:
         importlib.import_module(f"{__name__}.{name}")

@@ -548,6 +548,14 @@ def dropout_keep(n: int, p: float, seed: int, device) -> Tensor:
     return h >= _drop_threshold(p)
 
 
+def fold_dev_seed(base: int, counter: int) -> int:
+    """The host seed that draws the masks of ``DevSeed(base, counter)``: drop_base's mixing of
+    the device counter (csrc/kernels/drop_hash.hpp)."""
+    v = torch.tensor(((base & _M32) ^ ((counter * 0x9E3779B1 + 0x632BE5AB) & _M32)) & _M32,
+                     dtype=torch.int64)
+    return int(_mix32(v))
+
+
 def dropout_fwd(x: Tensor, p: float, seed: int) -> Tensor:
     if p <= 0.0:
         return x.clone()
@@ -938,3 +946,83 @@ def eval_stats(logits: Tensor, labels: Tensor, counters: Tensor,
         hist[0] += torch.bincount(b[~h], minlength=bins)
         hist[1] += torch.bincount(b[h], minlength=bins)
         hist[2].index_add_(0, b, torch.round(conf * EVAL_Q24).to(torch.int64))
+
+
+# ---- ConvNeXt block (csrc/kernels/dwconv7.hip)
+def _dw7_w(w: Tensor) -> Tensor:
+    """operand [C, 7, 7, 1] -> torch's depthwise filter [C, 1, 7, 7]"""
+    return _f(w).permute(0, 3, 1, 2)
+
+
+def dwconv7_fwd(x: Tensor, w: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """Depthwise 7x7, stride 1, pad 3: x [N, H, W, C], w [C, 7, 7, 1] (the operand layout of
+    ``gconv``), bias [C] -> y = T(b[c] + sum_{kh,kw} x[n, h+kh-3, w+kw-3, c] * w[c, kh, kw]);
+    taps outside the image contribute zero; fp32 accumulation, one rounding."""
+    C = x.shape[-1]
+    y = F.conv2d(_f(_nchw(x)), _dw7_w(w), None if bias is None else _f(bias), padding=3, groups=C)
+    return _nhwc(y).to(x.dtype)
+
+
+def dwconv7_dgrad(dy: Tensor, w: Tensor, addend: Optional[Tensor] = None) -> Tensor:
+    """dx = T(conv(dy, w mirrored) [+ addend]): a stride-1 "same" depthwise data-grad is a forward
+    convolution with the taps flipped; ``addend`` (dx's shape: the residual stream's gradient) is
+    added in fp32 before the single rounding."""
+    C = dy.shape[-1]
+    dx = _nhwc(F.conv2d(_f(_nchw(dy)), _dw7_w(w).flip(2, 3), None, padding=3, groups=C))
+    if addend is not None:
+        dx = dx + _f(addend)
+    return dx.to(dy.dtype)
+
+
+def dwconv7_wgrad(dy: Tensor, x: Tensor) -> Tuple[Tensor, Tensor]:
+    """(dw [C, 1, 7, 7], db [C]) in fp32 (fp64 inputs stay fp64):
+    dw[c, kh, kw] = sum dy[n, h, w, c] * x[n, h+kh-3, w+kw-3, c], db[c] = sum dy."""
+    N, H, W, C = x.shape
+    xp = F.pad(_f(x), (0, 0, 3, 3, 3, 3))
+    g = _f(dy)
+    dw = torch.stack([torch.stack([(g * xp[:, kh:kh + H, kw:kw + W]).sum((0, 1, 2))
+                                   for kw in range(7)], -1) for kh in range(7)], -2)
+    return dw.reshape(C, 1, 7, 7), g.reshape(-1, C).sum(0)
+
+
+def drop_path_keep(n: int, p: float, seed: int, device="cpu") -> Tensor:
+    """[n] keep mask of stochastic depth in "row" mode: the dropout hash (:func:`dropout_keep`)
+    applied to the sample index, so it depends only on (seed, sample)."""
+    if p <= 0.0:
+        return torch.ones(n, dtype=torch.bool, device=device)
+    return dropout_keep(n, p, seed, device)
+
+
+def _path_scale(f: Tensor, hw: int, p: float, seed: int) -> Tensor:
+    """s_n per row [R, 1]: fp32(1 / (1 - p)) where sample n = r / hw is kept, else 0 (p == 0: 1)."""
+    C = f.shape[-1]
+    n = f.numel() // C // hw
+    dt = torch.float64 if f.dtype == torch.float64 else torch.float32
+    if p <= 0.0:
+        return torch.ones(n * hw, 1, dtype=dt, device=f.device)
+    inv = torch.tensor(1.0 / (1.0 - p), dtype=torch.float32).to(dt)
+    s = drop_path_keep(n, p, seed, f.device).to(dt) * inv.to(f.device)
+    return s.repeat_interleave(hw).reshape(-1, 1)
+
+
+def scale_residual_fwd(f: Tensor, res: Tensor, gamma: Tensor, hw: int, p: float = 0.0,
+                       seed: int = 0) -> Tensor:
+    """out = T(fp32(res) + (fp32(f) * gamma[c]) * s_n): layer scale, stochastic depth by sample
+    (rows r of sample n = r / hw) and the residual add in three rounded fp32 operations."""
+    C = f.shape[-1]
+    s = _path_scale(f, hw, p, seed)
+    out = _f(res).reshape(-1, C) + (_f(f).reshape(-1, C) * _f(gamma).reshape(1, C)) * s
+    return out.reshape(f.shape).to(f.dtype)
+
+
+def scale_residual_bwd(dout: Tensor, f: Tensor, gamma: Tensor, hw: int, p: float = 0.0,
+                       seed: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
+    """(df, dgamma, dbias): df = T((fp32(dout) * gamma[c]) * s_n), dgamma[c] = sum_r (fp32(dout) *
+    fp32(f)) * s_n, dbias[c] = sum_r fp32(df) (the stored, rounded values: the bias gradient of
+    the Linear that produced f).  The residual's gradient is dout itself."""
+    C = f.shape[-1]
+    s = _path_scale(f, hw, p, seed)
+    d = _f(dout).reshape(-1, C)
+    df = ((d * _f(gamma).reshape(1, C)) * s).to(f.dtype)
+    dgamma = ((d * _f(f).reshape(-1, C)) * s).sum(0)
+    return df.reshape(f.shape), dgamma, _f(df).sum(0)

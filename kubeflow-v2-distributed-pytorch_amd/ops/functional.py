@@ -12,7 +12,9 @@ backward, SGD step) decomposes into these units, each one or two HIP launches:
   Mixup / CutMix), :func:`max_pool2d`, :func:`global_avg_pool`, :func:`layer_norm`,
   :func:`gelu`, :func:`attention`, :func:`embedding`;
 * :func:`patchify`, :func:`tokens_assemble` and :func:`add_layer_norm` — the Vision Transformer's
-  patch rows, its token assembly and the pre-LN residual stream kept inside the LayerNorm kernels.
+  patch rows, its token assembly and the pre-LN residual stream kept inside the LayerNorm kernels;
+* :func:`dwconv7` and :func:`scale_residual` — the ConvNeXt block's 7x7 depthwise convolution and
+  its closing layer scale + stochastic depth + residual add.
 
 Master weights stay fp32 (``nn.Parameter``); kernels consume a compute-dtype *shadow*
 (bf16 on the GPU) passed as a separate, non-differentiable argument; weight gradients come
@@ -1323,6 +1325,117 @@ def patchify(x: Tensor, patch: int, dtype: torch.dtype) -> Tensor:
     if x.requires_grad:
         raise ValueError("patchify has no backward: the input image takes no gradient")
     return K.patchify(x, patch, dtype)
+
+
+class _DwConv7Fn(Function):
+    """ConvNeXt's 7x7 depthwise convolution on the halo-resident kernels of dwconv7.hip.  The
+    data-grad adds the residual stream's gradient handed over through ``res_give``; the weight and
+    bias gradients accumulate straight into the flat DDP gradient buffer when the parameters live
+    there (fixed-order sums: no float atomics in any mode)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, w_c, bias, res_give):
+        y = K.dwconv7_fwd(x, w_c, None if bias is None else bias.detach())
+        ctx.save_for_backward(x, w_c)
+        ctx.weight, ctx.bias, ctx.res_give = weight, bias, res_give
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_c = ctx.saved_tensors
+        weight, bias = ctx.weight, ctx.bias
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            add = ctx.res_give.take() if ctx.res_give is not None else None
+            if add is not None:
+                add = add.reshape(dy.shape).to(dy.dtype)
+            dx = K.dwconv7_dgrad(dy, w_c, add)
+        need_w = ctx.needs_input_grad[1]
+        need_b = bias is not None and ctx.needs_input_grad[3]
+        if need_w or need_b:
+            native = K.use_native(dy)
+            tw = _direct_grad_target(weight) if native and need_w else None
+            tb = _direct_grad_target(bias) if native and need_b else None
+            g_w, g_b = K.dwconv7_wgrad(dy, x, None if tw is None else tw[1].reshape(-1),
+                                       None if tb is None else tb[1])
+            if tw is not None:
+                tw[0].grad_ready(weight)
+            elif need_w:
+                dw = g_w.reshape(weight.shape).to(weight.dtype)
+            if tb is not None:
+                tb[0].grad_ready(bias)
+            elif need_b:
+                db = g_b.to(bias.dtype)
+        return dx, dw, None, db, None
+
+
+def dwconv7(x: Tensor, weight: Tensor, w_c: Tensor, bias: Optional[Tensor],
+            res_give: Optional["ResidualSlot"] = None) -> Tensor:
+    """Depthwise 7x7, stride 1, pad 3 on NHWC ``x``; ``weight`` [C, 1, 7, 7] / ``bias``: the
+    parameters (gradient targets), ``w_c`` [C, 7, 7, 1]: the compute-dtype operand.
+    ``res_give``: x is also the residual of the block's closing :func:`scale_residual`, which was
+    given the same slot: that gradient is added in this layer's data-grad kernel."""
+    return _DwConv7Fn.apply(x, weight, w_c, bias, res_give)
+
+
+class _ScaleResidualFn(Function):
+    @staticmethod
+    def forward(ctx, f, res, gamma, p, seed, hw, bias_slot, res_give):
+        out = K.scale_residual_fwd(f, res, gamma.detach().reshape(-1), hw, p, seed)
+        ctx.save_for_backward(f)
+        ctx.gamma, ctx.conf = gamma, (p, seed, hw)
+        ctx.bias_slot, ctx.res_give = bias_slot, res_give
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (f,) = ctx.saved_tensors
+        gamma = ctx.gamma
+        p, seed, hw = ctx.conf
+        dout = dout.contiguous()
+        native = K.use_native(dout)
+        tg = _direct_grad_target(gamma) if native and ctx.needs_input_grad[2] else None
+        # the producing Linear's bias gradient, summed in this pass (native, flat space only)
+        slot, tbias = ctx.bias_slot, None
+        if native and slot is not None and slot.bias is not None:
+            tbias = _direct_grad_target(slot.bias, f.shape[-1])
+        df, dg, _ = K.scale_residual_bwd(dout, f, gamma.detach().reshape(-1), hw, p, seed,
+                                         None if tg is None else tg[1].reshape(-1),
+                                         None if tbias is None else tbias[1])
+        if tbias is not None:
+            slot.done = True
+        # d/d residual is dout itself; handed to the residual's other consumer when it adds it
+        dres = None
+        if ctx.needs_input_grad[1]:
+            dres = ctx.res_give.produce(dout) if ctx.res_give is not None else dout
+        if tg is not None:
+            tg[0].grad_ready(gamma)
+            dg = None
+        elif dg is not None:
+            dg = dg.reshape(gamma.shape).to(gamma.dtype) if ctx.needs_input_grad[2] else None
+        return df, dres, dg, None, None, None, None, None
+
+
+def scale_residual(f: Tensor, res: Tensor, gamma: Tensor, p: float, seed, training: bool,
+                   bias_slot: Optional[BiasGradSlot] = None,
+                   res_give: Optional["ResidualSlot"] = None) -> Tensor:
+    """``res + drop_path(gamma * f)``: ConvNeXt's layer scale, stochastic depth ("row" mode: a
+    whole sample is dropped with probability ``p`` and the kept ones are scaled by 1 / (1 - p))
+    and residual add in one kernel each way.  ``f`` / ``res`` [N, ..., C] (rows of sample n are
+    contiguous), ``gamma`` the fp32 ``layer_scale`` parameter ([C, 1, 1]).  The mask is the dropout
+    hash of (seed, sample) — ``seed`` an int or a :class:`K.DevSeed` — regenerated in the backward;
+    a batch whose samples are all dropped still runs every kernel and reports every gradient.
+    ``bias_slot``: f is the output of :func:`linear` given the same slot; this backward also sums
+    that layer's bias gradient.  ``res_give``: the residual's gradient goes to the slot (for
+    :func:`dwconv7` to add in its data-grad) instead of through autograd."""
+    if not training or p <= 0.0:
+        p, seed = 0.0, 0
+    elif not isinstance(seed, K.DevSeed):
+        seed = int(seed) & 0xFFFFFFFF
+    hw = f.numel() // f.shape[-1] // f.shape[0]
+    return _ScaleResidualFn.apply(f.contiguous(), res.contiguous(), gamma, float(p), seed, int(hw),
+                                  bias_slot, res_give)
 
 
 class _TokensAssembleFn(Function):

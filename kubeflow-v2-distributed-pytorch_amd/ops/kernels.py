@@ -26,7 +26,9 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "record_augment", "batch_erase_",
            "use_native",
            "gconv_fwd", "gconv_dgrad", "gconv_wgrad", "chan_stats", "affine_act",
-           "bn_generic_bwd_reduce", "bn_generic_bwd_apply", "avgpool2d_fwd", "avgpool2d_bwd"]
+           "bn_generic_bwd_reduce", "bn_generic_bwd_apply", "avgpool2d_fwd", "avgpool2d_bwd",
+           "dwconv7_fwd", "dwconv7_dgrad", "dwconv7_wgrad", "drop_path_keep",
+           "scale_residual_fwd", "scale_residual_bwd"]
 
 _ALLOW_REF_ON_GPU = os.environ.get("MIPIPE_ALLOW_REF_ON_GPU", "0") == "1"
 
@@ -542,7 +544,8 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, acc=None, drop=None, dbias=None, dsu
 def patchify(x, patch, dtype):
     """x [B, C, H, W] (fp32 / bf16, NCHW contiguous) -> [B*(H/P)*(W/P), C*P*P] in ``dtype``: the
     rows a P x P stride-P convolution multiplies with ``weight.view(D, C*P*P)``
-    (:func:`_ref.patchify` documents the order).  Native: P % 8 == 0, bf16 / fp32 output."""
+    (:func:`_ref.patchify` documents the order).  Native: P % 8 == 0 or P == 4 (ConvNeXt's stem),
+    bf16 / fp32 output."""
     if use_native(x):
         return native().patchify(x.contiguous(), int(patch), dtype)
     return _ref.patchify(x, patch, dtype)
@@ -837,3 +840,81 @@ def nchw_to_nhwc(x, dtype, pad_channels_to: int = 0):
     if pad_channels_to and C % pad_channels_to:
         y = torch.nn.functional.pad(y, (0, pad_channels_to - C % pad_channels_to))
     return y.contiguous().to(dtype)
+
+
+# ----------------------------------------------------------------------------- dwconv7.hip
+def dwconv7_fwd(x, w, bias=None):
+    """Depthwise 7x7 / stride 1 / pad 3 on NHWC ``x``: ``w`` [C, 7, 7, 1] in x's dtype (the operand
+    layout of :func:`gconv_fwd`, read as it stands), ``bias`` fp32 [C]
+    (:func:`_ref.dwconv7_fwd`).  Native: C % 8 == 0, C <= 2048."""
+    if use_native(x):
+        return native().dwconv7_fwd(x, w, bias)
+    return _ref.dwconv7_fwd(x, w, bias)
+
+
+def dwconv7_dgrad(dy, w, addend=None):
+    """dx of :func:`dwconv7_fwd`; ``addend`` (dx's shape and dtype: the residual stream's
+    gradient) is added in fp32 before the single rounding."""
+    if use_native(dy):
+        return native().dwconv7_dgrad(dy, w, None if addend is None else addend.contiguous())
+    return _ref.dwconv7_dgrad(dy, w, addend)
+
+
+def dwconv7_wgrad(dy, x, dw=None, dbias=None):
+    """-> (dw [C, 1, 7, 7], dbias [C]) fp32, ACCUMULATED into ``dw`` / ``dbias`` (flat-gradient
+    views; returned as None) when given.  Native: per-block partial rows summed in a fixed order,
+    no float atomics — the same bits on every launch, in every mode."""
+    if use_native(dy):
+        return native().dwconv7_wgrad(dy, x, dw, dbias)
+    g_w, g_b = _ref.dwconv7_wgrad(dy, x)
+    if dw is not None:
+        dw.add_(g_w.reshape(dw.shape).to(dw.dtype))
+        g_w = None
+    if dbias is not None:
+        dbias.add_(g_b.to(dbias.dtype))
+        g_b = None
+    return g_w, g_b
+
+
+def _path_seed(seed) -> int:
+    """The host seed of a stochastic-depth site (a :class:`DevSeed`'s counter folded in as the
+    kernels fold it)."""
+    if isinstance(seed, DevSeed):
+        return _ref.fold_dev_seed(seed.base, int(seed.counter.reshape(-1)[0].item()))
+    return int(seed) & 0xFFFFFFFF
+
+
+def drop_path_keep(n, p, seed, device="cpu"):
+    """[n] bool: the samples a stochastic-depth site with this seed keeps."""
+    return _ref.drop_path_keep(int(n), float(p), _path_seed(seed), device)
+
+
+def scale_residual_fwd(f, res, gamma, hw, p=0.0, seed=0):
+    """out = T(res + (f * gamma[c]) * s_n), s_n = keep_n / (1 - p) for the sample n = row / hw
+    (:func:`_ref.scale_residual_fwd`, bit for bit).  ``gamma``: fp32 [C]; ``seed``: int or
+    :class:`DevSeed`; p == 0: no drop."""
+    if use_native(f):
+        sd, dev = _split_seed(seed)
+        return native().scale_residual_fwd(f, res, gamma, int(hw), float(p), sd, dev)
+    return _ref.scale_residual_fwd(f, res, gamma, hw, p, _path_seed(seed))
+
+
+def scale_residual_bwd(dout, f, gamma, hw, p=0.0, seed=0, dgamma=None, dbias=None,
+                       want_bias=False):
+    """-> (df, dgamma, dbias) of :func:`scale_residual_fwd` in one pass over ``dout`` and ``f``;
+    the two column sums are ACCUMULATED into ``dgamma`` / ``dbias`` (fp32 [C] flat-gradient views;
+    returned as None) when given; dbias is computed only on request."""
+    if use_native(dout):
+        sd, dev = _split_seed(seed)
+        return native().scale_residual_bwd(dout, f, gamma, int(hw), float(p), sd, dev, dgamma,
+                                           dbias, bool(want_bias))
+    df, g_g, g_b = _ref.scale_residual_bwd(dout, f, gamma, hw, p, _path_seed(seed))
+    if dgamma is not None:
+        dgamma.add_(g_g.to(dgamma.dtype))
+        g_g = None
+    if dbias is not None:
+        dbias.add_(g_b.to(dbias.dtype))
+        g_b = None
+    elif not want_bias:
+        g_b = None
+    return df, g_g, g_b

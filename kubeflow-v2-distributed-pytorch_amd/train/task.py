@@ -283,6 +283,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="LARS trust coefficient")
     p.add_argument("--label-smoothing", type=float, default=0.0,
                    help="label smoothing of the training loss")
+    p.add_argument("--stochastic-depth", type=float, default=None, metavar="P",
+                   help="stochastic depth of the convnext_* models (default: the family's own "
+                        "value, e.g. 0.1 for convnext_tiny)")
     p.add_argument("--mixup-alpha", type=float, default=0.0,
                    help="Mixup: lambda ~ Beta(a, a); 0 = off")
     p.add_argument("--cutmix-alpha", type=float, default=0.0,
@@ -523,7 +526,23 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
             raise SystemExit(f"--arch {args.arch} needs square images, got {H}x{W}")
         kw["in_chans"] = C
         kw["image_size"] = H
+    stochastic_depth = None
+    if args.arch.startswith("convnext_"):
+        if H % 4 or W % 4 or min(H, W) < 32:
+            raise SystemExit(f"--arch {args.arch} needs images of at least 32x32 whose sides are "
+                             f"multiples of 4, got {H}x{W}")
+        if args.stochastic_depth is not None and not 0.0 <= args.stochastic_depth < 1.0:
+            raise SystemExit(f"--stochastic-depth must be in [0, 1), got {args.stochastic_depth}")
+        kw["in_chans"] = C
+        kw["stochastic_depth_prob"] = args.stochastic_depth
+        kw["seed"] = args.random_seed
+    elif args.stochastic_depth is not None:
+        raise SystemExit(f"--stochastic-depth applies to the convnext_* models only, not to "
+                         f"--arch {args.arch}")
     model = create_model(args.arch, **kw)
+    if args.arch.startswith("convnext_"):
+        stochastic_depth = model.stochastic_depth_prob
+        print(f"=> {args.arch}: stochastic depth {stochastic_depth:g}", flush=True)
     if args.pretrained:
         from mipipe.models import find_pretrained, load_pretrained
         wpath = find_pretrained(args.arch, args.pretrained_weights)
@@ -798,6 +817,8 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
                "backend": (torch.distributed.get_backend() if args.distributed else "none"),
                "hip_graph": bool(args.hip_graph), "deterministic": bool(args.deterministic),
                "fused_eval": fused}
+    if stochastic_depth is not None:
+        metrics["stochastic_depth"] = stochastic_depth
     if scheduled:
         metrics["lr"] = float(optimizer.last_lr().item())
     if mixer is not None:
