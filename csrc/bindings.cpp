@@ -2055,6 +2055,7 @@ void bind_loss(py::module& m);  // csrc/bind/loss.cpp: cross-entropy, top-1, eva
 void bind_data(py::module& m);  // csrc/bind/data.cpp: layout, synthetic data, records, batch mix
 void bind_vit(py::module& m);   // csrc/bind/vit.cpp: patchify, token assembly
 void bind_convnext(py::module& m);  // csrc/bind/convnext.cpp: dwconv7, scale_residual
+void bind_se(py::module& m);    // csrc/bind/se.cpp: bn_act_pool, se_scale
 }
 
 namespace mipipe_comm {
@@ -2070,6 +2071,7 @@ PYBIND11_MODULE(_C, m) {
   mipipe_bind::bind_data(m);
   mipipe_bind::bind_vit(m);
   mipipe_bind::bind_convnext(m);
+  mipipe_bind::bind_se(m);
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
         py::arg("shift") = py::none(), py::arg("slab_sum") = py::none(),
         py::arg("slab_sq") = py::none(), py::arg("bias") = py::none(), py::arg("relu") = false,

@@ -372,6 +372,70 @@ void pool_bn_bwd_apply(const void* dp, const uint8_t* idx, const void* pout, con
 void avgpool_fwd(const void* x, void* y, int N, int HW, int C, hipStream_t st, bool f32 = false);
 void avgpool_bwd(const void* dy, void* dx, int N, int HW, int C, hipStream_t st, bool f32 = false);
 
+// ---- squeeze-excitation and Hardswish (se.hip) -------------------------------------------------
+// NHWC x [N, HW, C], C % 8 == 0.  A block of kSeThreads threads owns tpr = min(C/8, kSeThreads)
+// 8-channel groups (grid.y walks wider tensors) and rpb = kSeThreads / tpr rows per pass, with
+// kSeRowU rows of loads in flight per thread.  A sample's HW rows are cut into `slices` slices of
+// `rows` rows (a multiple of rpb * kSeRowU; the last slice may be short) so that N * slices
+// reaches about kSeTargetBlocks blocks; a block takes (sample, slice) units grid-strided past
+// kSeMaxBlocks (kSeReduceBlocks for the BatchNorm reduction, whose blocks keep one partial row
+// each).  Per-sample sums go through [N, slices, C] partial rows summed in slice order, the
+// BatchNorm sums through per-block rows and det_sum_rows: no float atomics in any mode.
+constexpr int kSeThreads = 256;
+constexpr int kSeRowU = 4;
+constexpr int kSeTargetBlocks = 1024;
+constexpr int kSeMaxBlocks = 4096;
+constexpr int kSeReduceBlocks = 1024;
+constexpr int kSeActRelu = 1;       // vision.hip's code
+constexpr int kSeActHardswish = 3;
+struct SeSlices {
+  int tpr, rpb, cy;  // threads per row, rows per block pass, grid.y
+  int rows, slices;  // rows per slice, slices per sample
+};
+inline SeSlices se_slices(int N, int HW, int C) {
+  SeSlices g;
+  const int C8 = C / 8;
+  g.tpr = C8 < kSeThreads ? C8 : kSeThreads;
+  g.rpb = kSeThreads / g.tpr;
+  g.cy = (C8 + kSeThreads - 1) / kSeThreads;
+  const long unit = (long)g.rpb * kSeRowU;
+  const long smax = (HW + unit - 1) / unit;
+  long want = (kSeTargetBlocks + (long)N * g.cy - 1) / ((long)N * g.cy);
+  if (want > smax) want = smax;
+  if (want < 1) want = 1;
+  const long per = (HW + want - 1) / want;
+  g.rows = (int)((per + unit - 1) / unit * unit);
+  g.slices = (HW + g.rows - 1) / g.rows;
+  return g;
+}
+inline int se_reduce_rows(int N, int HW, int C) {
+  const long u = (long)N * se_slices(N, HW, C).slices;
+  return (int)(u < kSeReduceBlocks ? u : kSeReduceBlocks);
+}
+// z = T(act(y * scale[c] + bias[c])), act = kSeActRelu | kSeActHardswish; pm (may be null): fp32
+// [N, C] mean of the STORED z over the sample; ws: [N, slices, C] floats when pm and slices > 1
+void bn_act_pool_fwd(const void* y, const float* scale, const float* bias, void* z, float* pm,
+                     float* ws, int N, int HW, int C, int act, bool f32, hipStream_t st);
+// g = (dz + dpm[n, c] / HW) * act'(u), u recomputed from y (dpm may be null: no addend);
+// out_g[c] = sum g, out_gx[c] = sum g * xhat; ws: [2][se_reduce_rows][C] floats
+void bn_act_pool_bwd_reduce(const void* dz, const void* y, const float* scale, const float* bias,
+                            const float* mean, const float* invstd, const float* dpm, float* ws,
+                            float* out_g, float* out_gx, int N, int HW, int C, int act, bool f32,
+                            hipStream_t st);
+// dy = T(gamma invstd (g - sum_g / cnt - xhat sum_gx / cnt)), cnt = N * HW; sum_g null (eval-mode
+// statistics): dy = T(gamma invstd g)
+void bn_act_pool_bwd_apply(const void* dz, const void* y, const float* scale, const float* bias,
+                           const float* mean, const float* invstd, const float* gamma,
+                           const float* dpm, const float* sum_g, const float* sum_gx, void* dy,
+                           int N, int HW, int C, int act, bool f32, hipStream_t st);
+// out = T(z * hardsigmoid(gate[n, c])); gate [N, C] in T
+void se_scale_fwd(const void* z, const void* gate, void* out, int N, int HW, int C, bool f32,
+                  hipStream_t st);
+// dz = T(dout * hardsigmoid(gate)), dgate = T((sum_hw dout * z) * hardsigmoid'(gate));
+// ws: [N, slices, C] floats when slices > 1
+void se_scale_bwd(const void* dout, const void* z, const void* gate, void* dz, void* dgate,
+                  float* ws, int N, int HW, int C, bool f32, hipStream_t st);
+
 // ---- loss / data ------------------------------------------------------------------------------
 // work: 4 ints (valid-row count) then R floats (per-row losses, summed in a fixed order: the
 // loss is bit-reproducible)

@@ -28,13 +28,13 @@ def register_model(name: str, fn: Callable) -> None:
 
 
 _ZOO_MODULES = ("vgg", "mobilenet", "shufflenet", "squeezenet", "densenet", "inception", "bert", "vit",
-                "convnext")
+                "convnext", "mobilenetv3")
 
 
 def _lazy_register():
     """Import the remaining families (torchvision's registry: VGG/AlexNet, MobileNetV2, MNASNet,
     ShuffleNetV2, SqueezeNet, DenseNet, GoogLeNet, Inception-v3, the Vision Transformers,
-    ConvNeXt; plus BERT)."""
+    ConvNeXt, MobileNetV3; plus BERT)."""
     import importlib
     for name in _ZOO_MODULES:
         importlib.import_module(f"{__name__}.{name}")

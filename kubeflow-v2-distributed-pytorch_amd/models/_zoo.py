@@ -21,7 +21,8 @@ from mipipe import nn as mnn
 from mipipe.ops import functional as MF
 from mipipe.ops import kernels as K
 
-__all__ = ["ZooModel", "Exec", "run_seq", "run_module", "conv_bn", "act_of", "global_pool",
+__all__ = ["ZooModel", "Exec", "run_seq", "run_module", "conv_bn", "conv_bn_act_pool", "act_of",
+           "global_pool",
            "adaptive_avg_pool", "ref_linear"]
 
 
@@ -43,7 +44,33 @@ def act_of(m) -> str:
         return "relu6"
     if isinstance(m, tnn.ReLU):
         return "relu"
+    if isinstance(m, tnn.Hardswish):
+        return "hardswish"
     return "none"
+
+
+def conv_bn_act_pool(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, act: str,
+                     pool: bool = False):
+    """(z, pm): z = act(BN(conv(x))), act in {relu, hardswish}, through ``MF.bn_act_pool`` — the
+    activation recomputed from the conv output in the backward, and with ``pool`` the mean of z
+    over (h, w) ([N, C] fp32: a squeeze-excitation block's squeeze) from the same pass.  A dense
+    conv accumulates the batch statistics in its MFMA epilogue, other convs run the direct
+    kernel and a statistics pass."""
+    cin = x.shape[-1]
+    if conv.dense(cin) and conv.bias is None:
+        w_c = conv.kernel_weight(x.dtype, cin)
+        s, p = conv.stride[0], conv.mfma_pad()
+        if bn.training:
+            ws = MF.bn_workspace(bn, "fwd", x.device)
+            y, ps, pss = MF.conv2d(x, conv.weight, w_c, s, p, bn.running_mean,
+                                   None if ws is None else (ws[0], ws[1]))
+        else:
+            y, ps, pss = MF.conv2d(x, conv.weight, w_c, s, p)
+    else:
+        y = conv.run(x, "none")
+        ps, pss = K.chan_stats(y.detach(), bn.running_mean) if bn.training else (None, None)
+    st = MF.bn_stats_from_partials(ps, pss, y.numel() // y.shape[-1], bn, bn.training)
+    return MF.bn_act_pool(y, st, bn, act, pool)
 
 
 def conv_bn(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, act: str = "relu",
@@ -51,6 +78,10 @@ def conv_bn(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, act: str = 
     """act(BN(conv(x)) [+ residual]).  A dense conv accumulates the BN batch statistics in its
     MFMA epilogue and BN (+residual) (+ReLU) is one elementwise pass; other convs run the
     direct kernel, then the any-C BN pass."""
+    if act == "hardswish":
+        if residual is not None:
+            raise NotImplementedError("conv_bn: hardswish with a residual")
+        return conv_bn_act_pool(x, conv, bn, act)[0]
     cin = x.shape[-1]
     if conv.dense(cin) and act in ("none", "relu") and mnn.fused_eval_applies(bn):
         # fused evaluation: BN (+ conv bias) (+ residual) (+ ReLU) in the conv's epilogue
@@ -131,6 +162,8 @@ def run_module(m: tnn.Module, x: torch.Tensor, ex: Exec) -> torch.Tensor:
         return x.clamp(0.0, 6.0)
     if isinstance(m, tnn.ReLU):
         return torch.relu(x)
+    if isinstance(m, tnn.Hardswish):  # (the [N, 1280] classifier activation of MobileNetV3)
+        return F.hardswish(x)
     if isinstance(m, tnn.Dropout):
         return MF.dropout(x, m.p, ex.seed(), m.training)
     if isinstance(m, tnn.Identity):

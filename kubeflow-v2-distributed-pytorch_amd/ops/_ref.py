@@ -1026,3 +1026,121 @@ def scale_residual_bwd(dout: Tensor, f: Tensor, gamma: Tensor, hw: int, p: float
     df = ((d * _f(gamma).reshape(1, C)) * s).to(f.dtype)
     dgamma = ((d * _f(f).reshape(-1, C)) * s).sum(0)
     return df.reshape(f.shape), dgamma, _f(df).sum(0)
+
+
+# ----------------------------------------------------------------------------- se.hip
+def _cd(t: Tensor) -> torch.dtype:
+    return torch.float64 if t.dtype == torch.float64 else torch.float32
+
+
+def _const(v: float, like: Tensor) -> Tensor:
+    """A 0-dim constant on ``like``'s device: dividing by it is a true division on every backend
+    (a Python scalar divisor may become a multiplication by its reciprocal)."""
+    return torch.full((), v, dtype=like.dtype, device=like.device)
+
+
+def _recip(n: int, like: Tensor) -> Tensor:
+    """fp32(1 / n) (the double quotient rounded once), as the launchers compute it; the double
+    itself for float64 operands."""
+    return torch.tensor(1.0 / n, dtype=like.dtype).to(like.device)
+
+
+def _se_pre(y: Tensor, scale: Tensor, bias: Tensor) -> Tensor:
+    """u = (fp32(y) * scale[c]) + bias[c]: two rounded operations."""
+    dt = _cd(y)
+    return (_f(y) * scale.to(dt)) + bias.to(dt)
+
+
+def se_act(u: Tensor, act: str) -> Tensor:
+    """relu: max(u, 0); hardswish: (u * clamp(u + 3, 0, 6)) / 6 with a true division."""
+    if act == "relu":
+        return torch.relu(u)
+    if act == "hardswish":
+        return (u * (u + 3.0).clamp(0.0, 6.0)) / _const(6.0, u)
+    raise ValueError(f"bn_act_pool: act must be relu or hardswish, got {act!r}")
+
+
+def se_act_grad(u: Tensor, e: Tensor, act: str) -> Tensor:
+    """e * act'(u) by torch's rules at the knees (what ATen's backward kernels return).  relu:
+    u > 0.  hardswish: 0 for u <= -3, e * ((u / 3) + 0.5) for -3 < u < 3, e for u >= 3."""
+    zero = torch.zeros_like(e)
+    if act == "relu":
+        return torch.where(u > 0, e, zero)
+    if act == "hardswish":
+        mid = e * ((u / _const(3.0, u)) + 0.5)
+        return torch.where(u <= -3.0, zero, torch.where(u < 3.0, mid, e))
+    raise ValueError(f"bn_act_pool: act must be relu or hardswish, got {act!r}")
+
+
+def hardsigmoid(gate: Tensor) -> Tensor:
+    """s = clamp(fp32(gate) + 3, 0, 6) / 6."""
+    g = _f(gate)
+    return (g + 3.0).clamp(0.0, 6.0) / _const(6.0, g)
+
+
+def bn_act_pool_fwd(y: Tensor, scale: Tensor, bias: Tensor, act: str,
+                    want_pool: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+    """(z, pm): z = T(act(u)); pm [N, C] = (sum_hw fp32(z)) * (1 / HW) of the STORED z (what a
+    separate pool would have read), or None."""
+    N, H, W, C = y.shape
+    z = se_act(_se_pre(y, scale, bias), act).to(y.dtype)
+    if not want_pool:
+        return z, None
+    zf = _f(z)
+    return z, zf.reshape(N, H * W, C).sum(1) * _recip(H * W, zf)
+
+
+def _se_g(dz: Tensor, y: Tensor, scale: Tensor, bias: Tensor, act: str,
+          dpm: Optional[Tensor]) -> Tensor:
+    """g = e * act'(u), e = fp32(dz) + dpm[n, c] * (1 / HW) (the global pool's backward)."""
+    N, H, W, C = y.shape
+    e = _f(dz)
+    if dpm is not None:
+        e = e + (dpm.to(e.dtype).reshape(N, 1, 1, C) * _recip(H * W, e))
+    return se_act_grad(_se_pre(y, scale, bias), e, act)
+
+
+def bn_act_pool_bwd_reduce(dz: Tensor, y: Tensor, scale: Tensor, bias: Tensor, mean: Tensor,
+                           invstd: Tensor, act: str,
+                           dpm: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(sum g, sum g * xhat) per channel, xhat = (fp32(y) - mean[c]) * invstd[c]."""
+    C = y.shape[-1]
+    g = _se_g(dz, y, scale, bias, act, dpm)
+    xhat = (_f(y) - mean.to(g.dtype)) * invstd.to(g.dtype)
+    return g.reshape(-1, C).sum(0), (g * xhat).reshape(-1, C).sum(0)
+
+
+def bn_act_pool_bwd_apply(dz: Tensor, y: Tensor, scale: Tensor, bias: Tensor, mean: Tensor,
+                          invstd: Tensor, gamma: Tensor, act: str, dpm: Optional[Tensor] = None,
+                          sum_g: Optional[Tensor] = None,
+                          sum_gx: Optional[Tensor] = None) -> Tensor:
+    """dy = T((gamma * invstd) * ((g - sum_g * (1 / cnt)) - xhat * (sum_gx * (1 / cnt)))), cnt =
+    N * HW; without sums (eval-mode BN) dy = T((gamma * invstd) * g)."""
+    C = y.shape[-1]
+    g = _se_g(dz, y, scale, bias, act, dpm)
+    k = gamma.to(g.dtype) * invstd.to(g.dtype)
+    if sum_g is None:
+        return (k * g).to(dz.dtype)
+    inv = _recip(y.numel() // C, g)
+    xhat = (_f(y) - mean.to(g.dtype)) * invstd.to(g.dtype)
+    return (k * ((g - sum_g.to(g.dtype) * inv) - xhat * (sum_gx.to(g.dtype) * inv))).to(dz.dtype)
+
+
+def se_scale_fwd(z: Tensor, gate: Tensor) -> Tensor:
+    """out = T(fp32(z) * s), s = hardsigmoid(gate[n, c]); gate [N, C] or [N, 1, 1, C]."""
+    N, H, W, C = z.shape
+    return (_f(z) * hardsigmoid(gate).reshape(N, 1, 1, C)).to(z.dtype)
+
+
+def se_scale_bwd(dout: Tensor, z: Tensor, gate: Tensor) -> Tuple[Tensor, Tensor]:
+    """(dz, dgate): dz = T(fp32(dout) * s); dgate = T(q * s'), q[n, c] = sum_hw fp32(dout) *
+    fp32(z), s' = fp32(1 / 6) for -3 < gate < 3, else 0."""
+    N, H, W, C = z.shape
+    d = _f(dout)
+    dz = (d * hardsigmoid(gate).reshape(N, 1, 1, C)).to(z.dtype)
+    q = (d * _f(z)).reshape(N, H * W, C).sum(1)
+    gf = _f(gate).reshape(N, C)
+    # fp32(1 / 6) in every precision, as the kernel's constant and ATen's hardsigmoid backward
+    sixth = torch.tensor(1.0 / 6.0, dtype=torch.float32).to(device=gf.device, dtype=gf.dtype)
+    sp = torch.where((gf > -3.0) & (gf < 3.0), sixth, torch.zeros_like(sixth))
+    return dz, (q * sp).reshape(gate.shape).to(gate.dtype)

@@ -14,7 +14,10 @@ backward, SGD step) decomposes into these units, each one or two HIP launches:
 * :func:`patchify`, :func:`tokens_assemble` and :func:`add_layer_norm` — the Vision Transformer's
   patch rows, its token assembly and the pre-LN residual stream kept inside the LayerNorm kernels;
 * :func:`dwconv7` and :func:`scale_residual` — the ConvNeXt block's 7x7 depthwise convolution and
-  its closing layer scale + stochastic depth + residual add.
+  its closing layer scale + stochastic depth + residual add;
+* :func:`bn_act_pool` and :func:`se_scale` — BatchNorm + ReLU / Hardswish with the
+  squeeze-excitation block's global average pool in the same pass (and the pool's backward inside
+  the BatchNorm backward), and the block's Hardsigmoid gate multiply.
 
 Master weights stay fp32 (``nn.Parameter``); kernels consume a compute-dtype *shadow*
 (bf16 on the GPU) passed as a separate, non-differentiable argument; weight gradients come
@@ -1436,6 +1439,61 @@ def scale_residual(f: Tensor, res: Tensor, gamma: Tensor, p: float, seed, traini
     hw = f.numel() // f.shape[-1] // f.shape[0]
     return _ScaleResidualFn.apply(f.contiguous(), res.contiguous(), gamma, float(p), seed, int(hw),
                                   bias_slot, res_give)
+
+
+class _BNActPoolFn(Function):
+    """BatchNorm apply + ReLU / Hardswish (+ the global average pool of the result) in one pass
+    (se.hip); backward = one reduce + one apply pass that recompute the pre-activation from y and
+    take the pooled output's gradient as an addend."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, st, act, pool):
+        z, pm = K.bn_act_pool_fwd(y, st.scale, st.bias, act, pool)
+        ctx.save_for_backward(y, gamma)
+        ctx.st, ctx.act = st, act
+        return z, pm
+
+    @staticmethod
+    def backward(ctx, dz, dpm):
+        y, gamma = ctx.saved_tensors
+        st, act = ctx.st, ctx.act
+        dz = torch.zeros_like(y) if dz is None else dz.contiguous()
+        if dpm is not None:
+            dpm = dpm.contiguous()
+            if dpm.dtype != st.mean.dtype:
+                dpm = dpm.to(st.mean.dtype)
+        sg, sgx = K.bn_act_pool_bwd_reduce(dz, y, st.scale, st.bias, st.mean, st.invstd, act, dpm)
+        sums = (sg, sgx) if st.batch_stats else (None, None)
+        dy = K.bn_act_pool_bwd_apply(dz, y, st.scale, st.bias, st.mean, st.invstd,
+                                     gamma.detach().to(st.mean.dtype), act, dpm, *sums)
+        return dy, sgx.to(gamma.dtype), sg.to(gamma.dtype), None, None, None
+
+
+def bn_act_pool(y: Tensor, st: BNStats, bn, act: str, pool: bool = False):
+    """``(z, pm)``: z = act(BatchNorm(y)) for NHWC ``y`` with the statistics ``st`` (of the MFMA
+    conv epilogue, or :func:`K.chan_stats` + :func:`bn_stats_from_partials`), act in {relu,
+    hardswish}; with ``pool`` also pm [N, C] fp32, the mean of z over (h, w) — the
+    squeeze-excitation block's squeeze — else None.  The backward takes both gradients and makes
+    a single reduce + apply pair: the pool's backward is an addend inside them."""
+    return _BNActPoolFn.apply(y.contiguous(), bn.weight, bn.bias, st, act, bool(pool))
+
+
+class _SeScaleFn(Function):
+    @staticmethod
+    def forward(ctx, z, gate):
+        ctx.save_for_backward(z, gate)
+        return K.se_scale_fwd(z, gate)
+
+    @staticmethod
+    def backward(ctx, dout):
+        z, gate = ctx.saved_tensors
+        return K.se_scale_bwd(dout.contiguous(), z, gate)
+
+
+def se_scale(z: Tensor, gate: Tensor) -> Tensor:
+    """``z * hardsigmoid(gate)``: NHWC ``z``, ``gate`` [N, C] or [N, 1, 1, C] in z's dtype (the
+    squeeze-excitation block's excite); one kernel each way."""
+    return _SeScaleFn.apply(z.contiguous(), gate.contiguous())
 
 
 class _TokensAssembleFn(Function):

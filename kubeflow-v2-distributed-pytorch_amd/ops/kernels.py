@@ -28,7 +28,9 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "gconv_fwd", "gconv_dgrad", "gconv_wgrad", "chan_stats", "affine_act",
            "bn_generic_bwd_reduce", "bn_generic_bwd_apply", "avgpool2d_fwd", "avgpool2d_bwd",
            "dwconv7_fwd", "dwconv7_dgrad", "dwconv7_wgrad", "drop_path_keep",
-           "scale_residual_fwd", "scale_residual_bwd"]
+           "scale_residual_fwd", "scale_residual_bwd",
+           "bn_act_pool_fwd", "bn_act_pool_bwd_reduce", "bn_act_pool_bwd_apply", "se_scale_fwd",
+           "se_scale_bwd"]
 
 _ALLOW_REF_ON_GPU = os.environ.get("MIPIPE_ALLOW_REF_ON_GPU", "0") == "1"
 
@@ -918,3 +920,60 @@ def scale_residual_bwd(dout, f, gamma, hw, p=0.0, seed=0, dgamma=None, dbias=Non
     elif not want_bias:
         g_b = None
     return df, g_g, g_b
+
+
+# ----------------------------------------------------------------------------- se.hip
+_SE_ACT = {"relu": 1, "hardswish": 3}  # SE_ACT_RELU, SE_ACT_HARDSWISH
+
+
+def _se_act(act: str) -> int:
+    if act not in _SE_ACT:
+        raise ValueError(f"bn_act_pool: act must be relu or hardswish, got {act!r}")
+    return _SE_ACT[act]
+
+
+def bn_act_pool_fwd(y, scale, bias, act, want_pool=False):
+    """-> (z, pm): z = T(act(y * scale[c] + bias[c])) for NHWC ``y``, act in {relu, hardswish};
+    with ``want_pool`` also pm [N, C] fp32, the mean over (h, w) of the stored z — the SE block's
+    global average pool in the BatchNorm apply pass (:func:`_ref.bn_act_pool_fwd`, z bit for
+    bit).  Native: C % 8 == 0."""
+    if use_native(y):
+        return native().bn_act_pool_fwd(y, scale, bias, _se_act(act), bool(want_pool))
+    return _ref.bn_act_pool_fwd(y, scale, bias, act, want_pool)
+
+
+def bn_act_pool_bwd_reduce(dz, y, scale, bias, mean, invstd, act, dpm=None):
+    """-> (sum g, sum g * xhat) fp32 [C]: g = (dz + dpm[n, c] / HW) * act'(u) with the
+    pre-activation u recomputed from ``y``; ``dpm`` [N, C] fp32 is the pooled output's gradient
+    (None: no addend).  Native: per-block partial rows summed in a fixed order."""
+    if use_native(dz):
+        return native().bn_act_pool_bwd_reduce(dz, y, scale, bias, mean, invstd, _se_act(act), dpm)
+    return _ref.bn_act_pool_bwd_reduce(dz, y, scale, bias, mean, invstd, act, dpm)
+
+
+def bn_act_pool_bwd_apply(dz, y, scale, bias, mean, invstd, gamma, act, dpm=None, sum_g=None,
+                          sum_gx=None):
+    """dy of the BatchNorm behind :func:`bn_act_pool_fwd` from the sums of
+    :func:`bn_act_pool_bwd_reduce`; without sums (eval-mode statistics) dy = gamma invstd g
+    (:func:`_ref.bn_act_pool_bwd_apply`, bit for bit)."""
+    if use_native(dz):
+        return native().bn_act_pool_bwd_apply(dz, y, scale, bias, mean, invstd, gamma,
+                                              _se_act(act), dpm, sum_g, sum_gx)
+    return _ref.bn_act_pool_bwd_apply(dz, y, scale, bias, mean, invstd, gamma, act, dpm, sum_g,
+                                      sum_gx)
+
+
+def se_scale_fwd(z, gate):
+    """out = T(z * hardsigmoid(gate[n, c])): NHWC ``z``, ``gate`` [N, C] or [N, 1, 1, C] in z's
+    dtype (:func:`_ref.se_scale_fwd`, bit for bit)."""
+    if use_native(z):
+        return native().se_scale_fwd(z, gate)
+    return _ref.se_scale_fwd(z, gate)
+
+
+def se_scale_bwd(dout, z, gate):
+    """-> (dz, dgate) of :func:`se_scale_fwd` in one pass over ``dout`` and ``z``; dgate has
+    gate's shape and dtype."""
+    if use_native(dout):
+        return native().se_scale_bwd(dout, z, gate)
+    return _ref.se_scale_bwd(dout, z, gate)
