@@ -135,6 +135,11 @@ void eval_stats(Tensor logits, Tensor labels, Tensor counters, optional<Tensor> 
 }  // namespace
 
 void bind_loss(py::module& m) {
+  // launch constants of loss.hip (launchers.hpp), for the edge tests
+  m.attr("CE_THREADS") = mipipe::kCeThreads;
+  m.attr("CE_VEC") = mipipe::kCeVec;
+  m.attr("CE_BWD_MAX_GRID_ROWS") = mipipe::kCeBwdMaxGridRows;
+  m.attr("TOP1_ROWS_PER_BLOCK") = mipipe::kTop1RowsPerBlock;
   m.def("cross_entropy_fwd", &cross_entropy_fwd, py::arg("logits"), py::arg("labels"),
         py::arg("smoothing") = 0.0, py::arg("ignore_index") = -100, py::arg("valid_cols") = -1);
   m.def("cross_entropy_bwd", &cross_entropy_bwd, py::arg("logits"), py::arg("labels"),

@@ -437,6 +437,19 @@ void se_scale_bwd(const void* dout, const void* z, const void* gate, void* dz, v
                   float* ws, int N, int HW, int C, bool f32, hipStream_t st);
 
 // ---- loss / data ------------------------------------------------------------------------------
+// Launch constants of loss.hip, exported to Python (CE_* / TOP1_*) so that the edge tests derive
+// their shapes from the values the kernels use.  Cross-entropy: blocks of kCeThreads threads, one
+// block per row in the forward; where V % kCeVec == 0 a thread takes kCeVec columns per 16-byte
+// item.  ce_bwd's grid is (column blocks, rows) with at most kCeBwdMaxGridRows rows in grid.y
+// (the hardware's limit), a block walking further rows at that stride.  top1_correct: one wave
+// per row, kTop1RowsPerBlock rows per block.
+constexpr int kCeThreads = 256;
+constexpr int kCeVec = 8;
+constexpr int kCeBwdMaxGridRows = 65535;
+constexpr int kTop1RowsPerBlock = 4;
+// Labels: a hard label other than ignore_index that is outside [0, valid_cols) — and either label
+// of a pair target — reads nothing: its logit counts as 0, no column gets its target, and the
+// row still counts in the mean.
 // work: 4 ints (valid-row count) then R floats (per-row losses, summed in a fixed order: the
 // loss is bit-reproducible)
 void cross_entropy_fwd_bwd(const void* logits, const int64_t* labels, float* loss, void* grad,

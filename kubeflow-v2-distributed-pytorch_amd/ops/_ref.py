@@ -207,7 +207,10 @@ def cross_entropy_fwd_bwd(logits: Tensor, labels: Tensor, label_smoothing: float
                           ignore_index: int = -100,
                           valid_cols: int = -1) -> Tuple[Tensor, Tensor]:
     """Mean CE over non-ignored rows and its gradient wrt logits (for grad_output = 1).
-    ``valid_cols`` > 0: only the first columns are classes; the gradient of the rest is 0."""
+    ``valid_cols`` > 0: only the first columns are classes; the gradient of the rest is 0.
+    A label other than ``ignore_index`` that is outside the classes reads nothing, as in the
+    pair-target form: its logit counts as 0 (the row's loss is its log-sum-exp), no column gets
+    the ``1 - label_smoothing`` target, and the row still counts in the mean."""
     V = logits.shape[-1]
     if 0 < valid_cols < V:
         loss, g = cross_entropy_fwd_bwd(logits[:, :valid_cols], labels, label_smoothing,
@@ -217,14 +220,15 @@ def cross_entropy_fwd_bwd(logits: Tensor, labels: Tensor, label_smoothing: float
     valid = labels != ignore_index
     n = valid.sum().clamp_min(1)
     logp = torch.log_softmax(lf, dim=-1)
-    safe = labels.clamp_min(0).long()
-    nll = -logp.gather(1, safe[:, None])[:, 0]
+    inside = valid & (labels >= 0) & (labels < V)
+    safe = torch.where(inside, labels, torch.zeros_like(labels)).long()
+    nll = torch.where(inside, -logp.gather(1, safe[:, None])[:, 0], torch.logsumexp(lf, dim=-1))
     if label_smoothing > 0:
         smooth = -logp.mean(dim=-1)
         nll = (1 - label_smoothing) * nll + label_smoothing * smooth
-    loss = (nll * valid).sum() / n
+    loss = torch.where(valid, nll, torch.zeros_like(nll)).sum() / n
     p = logp.exp()
-    oh = F.one_hot(safe, lf.shape[-1]).float()
+    oh = F.one_hot(safe, lf.shape[-1]).float() * inside[:, None]
     if label_smoothing > 0:
         oh = oh * (1 - label_smoothing) + label_smoothing / lf.shape[-1]
     grad = (p - oh) * valid[:, None] / n
@@ -239,7 +243,8 @@ def cross_entropy_mixed_fwd_bwd(logits: Tensor, labels: Tensor, mix: Tensor,
     mix[0]`` (the batch-mix descriptor, :mod:`mipipe.data.mix`) and ``eps = label_smoothing``
     the target is ``t[c] = eps/Vv + (1-eps) * (lam*[c==a] + (1-lam)*[c==b])`` and the loss the
     mean over all rows of ``lse - sum(t * x)``.  There is no ``ignore_index`` in this form: every
-    row counts.  ``valid_cols`` as in :func:`cross_entropy_fwd_bwd`."""
+    row counts.  A label outside the classes reads nothing: it matches no column.
+    ``valid_cols`` as in :func:`cross_entropy_fwd_bwd`."""
     V = logits.shape[-1]
     if 0 < valid_cols < V:
         loss, g = cross_entropy_mixed_fwd_bwd(logits[:, :valid_cols], labels, mix,
@@ -250,10 +255,15 @@ def cross_entropy_mixed_fwd_bwd(logits: Tensor, labels: Tensor, mix: Tensor,
     lam = mix.reshape(-1)[0].to(lf.dtype)
     a = labels.long()
     b = a.flip(0)
-    t = lam * F.one_hot(a, V).to(lf.dtype) + (1 - lam) * F.one_hot(b, V).to(lf.dtype)
+    cols = torch.arange(V, device=lf.device)
+    t = lam * (cols == a[:, None]).to(lf.dtype) + (1 - lam) * (cols == b[:, None]).to(lf.dtype)
     t = t * (1 - label_smoothing) + label_smoothing / V
     logp = torch.log_softmax(lf, dim=-1)
-    loss = -(t * logp).sum() / max(1, R)
+    # lse - sum(t * x): -sum(t * logp) while the labels are classes (sum(t) = 1); a label that
+    # is none takes its weight's logit as 0.  A column without target weight enters nothing (a
+    # masked class: 0 * -inf would be nan).
+    tx = torch.where(t != 0, t * lf, torch.zeros_like(lf)).sum(-1)
+    loss = (torch.logsumexp(lf, dim=-1) - tx).sum() / max(1, R)
     grad = (logp.exp() - t) / max(1, R)
     return loss, grad.to(logits.dtype)
 

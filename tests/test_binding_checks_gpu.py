@@ -142,6 +142,21 @@ def test_ce_family_accepts(nat):
               ref_grad)
 
 
+@pytest.mark.parametrize("last", [-1, 11, V, V + 5])
+def test_ce_hard_labels_outside_the_classes_accept(nat, last):
+    """A hard label that is no class (and not ignore_index) is no error and reads nothing: -1,
+    valid_cols (a padding column), V and V + 5, on the first rows and on the last."""
+    logits, labels = _ce_inputs()
+    labels = torch.tensor([-1, 11, V, last], device="cuda")
+    ref_loss, ref_grad = _ref.cross_entropy_fwd_bwd(logits, labels, 0.0, -100, 11)
+    loss, work = nat.cross_entropy_fwd(logits, labels, 0.0, -100, 11)
+    assert int(work[0]) == R
+    _close_ce(loss, nat.cross_entropy_bwd(logits, labels, work, _gout(), 0.0, -100, 11), ref_loss,
+              ref_grad)
+    _close_ce(*nat.cross_entropy_fwd_bwd(logits, labels, 0.0, -100, 11), ref_loss, ref_grad)
+    assert torch.isfinite(loss) and not ref_grad[:, 11:].any()
+
+
 def test_metrics_accept(nat):
     logits, labels = _ce_inputs()
     labels = logits.float().argmax(1).where(torch.arange(R, device="cuda") % 2 == 0, labels)
