@@ -269,8 +269,10 @@ __global__ __launch_bounds__(C::THREADS, (conv_occ<T, C>())) void conv_fwd_kerne
     ws.det_rows = 1;
     epilogue_f32<BM, BN, true, C::WM, C::WN, C::PP>(smem, acc, ws, m0, n0, wave, lane);
   } else {
-    epilogue_out<BM, BN, DGRAD_EPI, T, C::WM, C::WN, false, C::PP>(smem, acc, e, m0, n0, 0, wave,
-                                                                   lane);
+    // (a forward stores row m at row m; a forward-style data-grad class may remap its rows)
+    constexpr int kOpt = kEpiNoAux | (DGRAD_EPI ? 0 : kEpiNoRemap | kEpiStatsEarly);
+    epilogue_out<BM, BN, DGRAD_EPI, T, C::WM, C::WN, false, C::PP, kOpt>(smem, acc, e, m0, n0, 0,
+                                                                         wave, lane);
   }
 }
 
@@ -325,7 +327,8 @@ __global__ __launch_bounds__(C::THREADS) void conv_splitk_finish_kernel(
         acc[i][j] += f32x4{v.x, v.y, v.z, v.w};
       }
   }
-  epilogue_out<BM, BN, FUSE, T, WM, WN, false, false>(smem, acc, e, m0, n0, 0, wave, lane);
+  constexpr int kOpt = kEpiNoAux | (FUSE ? 0 : kEpiNoRemap | kEpiStatsEarly);
+  epilogue_out<BM, BN, FUSE, T, WM, WN, false, false, kOpt>(smem, acc, e, m0, n0, 0, wave, lane);
 }
 
 // TWO: BN-backward fusion of a two-branch block output (dense bf16 data-grads only)
@@ -355,7 +358,8 @@ __global__ __launch_bounds__(C::THREADS, (conv_occ<T, C>())) void conv_dgrad_ker
   };
   f32x4 acc[BM / C::WM / 16][BN / C::WN / 16];
   run_main_loop<T, C, PA, PB>(smem, ia, ib, m0, n0, 0, nk, acc, wave, lane);
-  epilogue_out<BM, BN, true, T, C::WM, C::WN, TWO, C::PP>(smem, acc, e, m0, n0, 0, wave, lane);
+  epilogue_out<BM, BN, true, T, C::WM, C::WN, TWO, C::PP, kEpiNoAux>(smem, acc, e, m0, n0, 0, wave,
+                                                                     lane);
 }
 
 // ATOMIC: split-K partial tiles added with fp32 atomics; else the block owns its output tile

@@ -366,48 +366,87 @@ constexpr bool kMfmaStats = true;
 #else
 constexpr bool kMfmaStats = false;
 #endif
-template <int BM, int BN, int NWV>
+// 16-column groups a wave owns (group cg = wave + c * NWV) and the statistics shift of this lane's
+// column in each.  The convolution forwards (kEpiStatsEarly) request it BEFORE the tile is staged:
+// the load's latency hides under the staging and its barriers instead of standing between the
+// MFMAs and the partial sums' stores.  That early load is unconditional (the zero line when there
+// are no statistics; clamped column): a load behind a run-time branch is closed by a full
+// vmcnt(0) drain (see EpiOps).  Every other kernel loads it at the statistics call.
+template <int BN, int NWV>
+constexpr int kStatsGroups() { return (BN / 16 + NWV - 1) / NWV; }
+template <int BN, int NWV>
+__device__ __forceinline__ void stats_shift_load(const EpiParams& e, uint32_t n0, int wave,
+                                                 int lane, float (&sh)[kStatsGroups<BN, NWV>()]) {
+  const bool has = e.st_sum != nullptr;
+  const float* sp = has ? e.st_shift : reinterpret_cast<const float*>(g_epi_zero);
+#pragma unroll
+  for (int c = 0; c < kStatsGroups<BN, NWV>(); ++c) {
+    const int cg = wave + c * NWV;
+    const uint32_t n = n0 + (uint32_t)cg * 16 + ((uint32_t)lane & 15);
+    sh[c] = sp[(has && cg < BN / 16 && n < e.N) ? n : 0];
+  }
+}
+// FAST: full tiles take a copy of the MFMA chains without row masks (one wave-uniform branch);
+// otherwise one masked copy serves both (a mask over a full tile changes nothing).
+template <int BM, int BN, int NWV, bool FAST>
 __device__ __forceinline__ void stats_mfma(const char* smem, const EpiParams& e, uint32_t m0,
-                                           uint32_t n0, int wave, int lane) {
+                                           uint32_t n0, int wave, int lane,
+                                           const float (&sh)[kStatsGroups<BN, NWV>()]) {
   constexpr int P = kEpiPitch<BN, __bf16>();
-  constexpr int NCG = BN / 16, NKC = BM / 32;
+  constexpr int NCG = BN / 16, NKC = BM / 32, CGW = kStatsGroups<BN, NWV>();
   static_assert(BN % 16 == 0 && BM % 32 == 0, "MFMA statistics tile");
   const uint32_t g = (uint32_t)lane >> 4, q4 = ((uint32_t)lane & 15) >> 2, p = (uint32_t)lane & 3;
   bf16x8 ones;
 #pragma unroll
   for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
   const uint32_t nv = e.M - m0 < (uint32_t)BM ? e.M - m0 : (uint32_t)BM;
-  for (int cg = wave; cg < NCG; cg += NWV) {  // wave-uniform
-    f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-    const uint32_t ch = (uint32_t)cg * 2 + (p >> 1);  // 8-column chunk of this lane's reads
+  // every group's MFMA chains first (independent chains: they overlap), the scalarised tails
+  // after them.  FULL tiles (one wave-uniform branch, outside the loops) run without row masks.
+  f32x4 s1[CGW], s2[CGW];
+  auto sums = [&](auto full_tag) {
+    constexpr bool FULL = decltype(full_tag)::value;
 #pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      const char* a0 = smem + (kc * 32 + 8 * g + q4) * P + ch * 16 + 8 * (p & 1);
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 4 * P));
-      typedef __attribute__((ext_vector_type(8))) short s16x8;
-      const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      bf16x8 y = __builtin_bit_cast(bf16x8, v);
-      if (nv < (uint32_t)BM) {  // partial tile (wave-uniform): rows past M add nothing, whatever
-        // was staged there (a bias, say); this lane's 8 values are rows kc*32 + 8g + 0..7
+    for (int c = 0; c < CGW; ++c) {
+      s1[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+      s2[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const int cg = wave + c * NWV;  // wave-uniform
+      if (cg >= NCG) continue;
+      const uint32_t ch = (uint32_t)cg * 2 + (p >> 1);  // 8-column chunk of this lane's reads
 #pragma unroll
-        for (int r = 0; r < 8; ++r)
-          if ((uint32_t)(kc * 32) + 8 * g + (uint32_t)r >= nv) y[r] = (__bf16)0.0f;
+      for (int kc = 0; kc < NKC; ++kc) {
+        const char* a0 = smem + (kc * 32 + 8 * g + q4) * P + ch * 16 + 8 * (p & 1);
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 4 * P));
+        typedef __attribute__((ext_vector_type(8))) short s16x8;
+        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        bf16x8 y = __builtin_bit_cast(bf16x8, v);
+        if constexpr (!FULL) {  // partial tile: rows past M add nothing, whatever was staged
+          // there (a bias, say); this lane's 8 values are rows kc*32 + 8g + 0..7
+#pragma unroll
+          for (int r = 0; r < 8; ++r)
+            if ((uint32_t)(kc * 32) + 8 * g + (uint32_t)r >= nv) y[r] = (__bf16)0.0f;
+        }
+        s1[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, y, s1[c], 0, 0, 0);  // rows: Σ_k Y[k][j]
+        s2[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(y, y, s2[c], 0, 0, 0);     // Σ_k Y[k][i] Y[k][j]
       }
-      s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, y, s1, 0, 0, 0);  // rows: Σ_k Y[k][j]
-      s2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(y, y, s2, 0, 0, 0);     // Σ_k Y[k][i] Y[k][j]
     }
-    // lane holds D[i = 4(lane>>4) + q][j = lane & 15]: column j's diagonal sits at q = j & 3 of
-    // the lane with lane >> 4 == j >> 2 (which also holds its column sum)
-    const uint32_t j = (uint32_t)lane & 15;
-    if (g == (j >> 2)) {
+  };
+  if (FAST && nv == (uint32_t)BM) sums(std::true_type());
+  else sums(std::false_type());
+  // lane holds D[i = 4(lane>>4) + q][j = lane & 15]: column j's diagonal sits at q = j & 3 of
+  // the lane with lane >> 4 == j >> 2 (which also holds its column sum)
+  const uint32_t j = (uint32_t)lane & 15;
+  if (g == (j >> 2)) {
+    const int q = (int)(j & 3);
+    const double nd = (double)nv;
+#pragma unroll
+    for (int c = 0; c < CGW; ++c) {
+      const int cg = wave + c * NWV;
       const uint32_t n = n0 + (uint32_t)cg * 16 + j;
-      if (n < e.N) {
-        const int q = (int)(j & 3);
-        const double sy = (double)s1[q], syy = (double)s2[q], sh = (double)e.st_shift[n];
-        const double nd = (double)nv;
-        const float a = (float)(sy - nd * sh);
-        const float b = (float)(syy - 2.0 * sh * sy + nd * sh * sh);
+      if (cg < NCG && n < e.N) {
+        const double sy = (double)s1[c][q], syy = (double)s2[c][q], shd = (double)sh[c];
+        const float a = (float)(sy - nd * shd);
+        const float b = (float)(syy - 2.0 * shd * sy + nd * shd * shd);
         if (e.det_rows > 0) {
           const long row = (long)(e.det_row0 + m0 / BM) * e.N + n;
           e.st_sum[row] = a;
@@ -422,13 +461,24 @@ __device__ __forceinline__ void stats_mfma(const char* smem, const EpiParams& e,
   }
 }
 
+// Compile-time options of epilogue_out's plain store loop (OPT): what a caller never uses.
+constexpr int kEpiNoAux = 1;    // e.aux (the GELU Linear's second output) is never set
+constexpr int kEpiNoRemap = 2;  // e.rm_s is always 0: output row m is stored at row m
+// MFMA statistics of a kernel that really runs them (the convolution forwards): shift loaded
+// before the staging, mask-free full-tile path, and the statistics AFTER the output stores
+// (plain store loop only: !FUSE)
+constexpr int kEpiStatsEarly = 4;
+
 // Output in the activation dtype T (bf16, or fp32 on the reference-precision path).
 // acc layout: lane holds C[m][n..n+3] for tile (i, j).
 // FUSE: compile the dgrad fusions (addend / BN-backward reduction); kernels that never use
 // them keep their register budget.  early: an operand ring the kernel already primed.
 // TWO: the BN-backward fusion of a two-branch block output (e.bnr_y2 set, FUSE only).
+// OPT: kEpiNoAux / kEpiNoRemap / kEpiStatsEarly.  The convolution kernels never store an aux
+// output, and a forward's rows are never remapped: their store loop then holds no GELU code (8 erf expansions
+// per 16-B chunk, in every unrolled iteration) and no per-row remap branch.
 template <int BM, int BN, bool FUSE = false, class T = __bf16, int WM = 2, int WN = 2,
-          bool TWO = false, bool HALVES = false>
+          bool TWO = false, bool HALVES = false, int OPT = 0>
 __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16],
                              const EpiParams& e, uint32_t m0, uint32_t n0, uint32_t prow_base,
                              int wave, int lane,
@@ -578,6 +628,12 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
       }
     }
   }
+  // MFMA statistics: this lane's shifts, in flight across the staging
+  constexpr int NWV = kThreads / 64;
+  float st_sh[kStatsGroups<BN, NWV>()];
+  constexpr bool SEARLY = MSTATS && (OPT & kEpiStatsEarly) != 0;
+  static_assert(!SEARLY || !FUSE, "statistics after the stores: plain store loop only");
+  if constexpr (SEARLY) stats_shift_load<BN, NWV>(e, n0, wave, lane, st_sh);
   // every wave is past the main loop (whose LDS the staging tile overwrites) and the
   // statistics partials are in LDS
   lds_barrier();
@@ -599,8 +655,16 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
     }
   if (early == nullptr) ops.prime(e, m0, n0);  // accumulators are dead now
   lds_barrier();
+  // The MFMA statistics only read the staged tile, so the output stores need not wait for them:
+  // with kEpiStatsEarly (plain store loop: nothing overwrites the tile after it) they run after
+  // the stores are issued.  Elsewhere (the fused loop's column sums reuse the tile's LDS) they
+  // stay in front.
+  const bool fused = FUSE && (has_add || bnr);
   if (MSTATS && e.st_sum != nullptr) {
-    stats_mfma<BM, BN, kThreads / 64>(smem, e, m0, n0, wave, lane);
+    if constexpr (!SEARLY) {
+      stats_shift_load<BN, NWV>(e, n0, wave, lane, st_sh);
+      stats_mfma<BM, BN, NWV, false>(smem, e, m0, n0, wave, lane, st_sh);
+    }
   } else if (e.st_sum != nullptr) {
     // one fp32 atomic per column per block into replica row blockIdx % st_R (fire and forget:
     // no barrier below waits for them)
@@ -625,7 +689,7 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
   float sg[8], sgx[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) sg[q] = sgx[q] = 0.f;
-  if (FUSE && (has_add || bnr)) {
+  if (fused) {
     // fused loop: the ring's next loads are issued unconditionally (absent streams read the
     // zero line), so hipcc keeps PF iterations of loads in flight with counted waits
 #pragma unroll
@@ -688,12 +752,12 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
       const uint32_t r = c / CPR, cc = c % CPR;
       const uint32_t m = m0 + r, n = n0 + cc * 8;
       if (m < e.M && n < e.N) {
-        const long orow = out_row(e, m);
+        const long orow = (OPT & kEpiNoRemap) != 0 ? (long)m : out_row(e, m);
 #pragma unroll
         for (int h = 0; h < (int)(sizeof(T) / 2); ++h) {
           uint4 v = *reinterpret_cast<const uint4*>(smem + r * P + cc * 8 * sizeof(T) + 16 * h);
           uint4* dst = reinterpret_cast<uint4*>(C + orow * e.ldc + n) + h;
-          if constexpr (!std::is_same<T, float>::value) {
+          if constexpr (!std::is_same<T, float>::value && (OPT & kEpiNoAux) == 0) {
             if (e.aux != nullptr) {  // GELU Linear: h to aux, gelu(h) (bf16-rounded h, as the
               // gelu_fwd kernel computes it) to C
               reinterpret_cast<uint4*>(reinterpret_cast<T*>(e.aux) + orow * e.ldc + n)[h] = v;
@@ -711,6 +775,9 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
           }
         }
       }
+    }
+    if constexpr (SEARLY) {
+      if (e.st_sum != nullptr) stats_mfma<BM, BN, NWV, true>(smem, e, m0, n0, wave, lane, st_sh);
     }
   }
   if (FUSE && bnr) {
