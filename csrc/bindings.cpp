@@ -360,7 +360,7 @@ Tensor conv_dgrad(Tensor dy, Tensor w, std::vector<int64_t> x_shape, int stride,
                   optional<Tensor> bn_invstd, optional<Tensor> bn_scale, optional<Tensor> bn_bias,
                   optional<Tensor> bn_rep, optional<Tensor> bn_z, int pad_w, int cfg,
                   optional<Tensor> bn_mask, optional<Tensor> bn_y2, optional<Tensor> bn_mean2,
-                  optional<Tensor> bn_invstd2, optional<Tensor> wflip_pre) {
+                  optional<Tensor> bn_invstd2, optional<Tensor> wflip_pre, bool generic_epi) {
   check_act(dy, "dy");
   check_same(w, dy, "w");
   c10::DeviceGuard g(dy.device());
@@ -469,7 +469,7 @@ Tensor conv_dgrad(Tensor dy, Tensor w, std::vector<int64_t> x_shape, int stride,
       }
       Tensor ws = dgrad_ws(c);
       mipipe::conv_dgrad(dy.data_ptr(), w.data_ptr(), dxs.data_ptr(), s, stream(),
-                         any ? &f2 : nullptr, c, wfp, preflipped, wsp(ws));
+                         any ? &f2 : nullptr, c, wfp, preflipped, wsp(ws), generic_epi);
     });
   }
   Tensor ws = dgrad_ws(cfg);
@@ -481,7 +481,7 @@ Tensor conv_dgrad(Tensor dy, Tensor w, std::vector<int64_t> x_shape, int stride,
     fz.bn_rep = part.data_ptr<float>();
     fz.det_rows = P;
     mipipe::conv_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), s, stream(), &fz, cfg, wfp,
-                       preflipped, wsp(ws));
+                       preflipped, wsp(ws), generic_epi);
     const long rs = (long)mipipe::kStatReplicas * s.Ci, ps = (long)P * s.Ci;
     mipipe::det_sum_rows(fz.bn_rep, fz.bn_rep + ps, P, s.Ci, rep, rep + rs, false, stream());
     if (two)
@@ -490,7 +490,7 @@ Tensor conv_dgrad(Tensor dy, Tensor w, std::vector<int64_t> x_shape, int stride,
     return dx;
   }
   mipipe::conv_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), s, stream(), any ? &fz : nullptr,
-                     cfg, wfp, preflipped, wsp(ws));
+                     cfg, wfp, preflipped, wsp(ws), generic_epi);
   return dx;
 }
 
@@ -2113,7 +2113,15 @@ PYBIND11_MODULE(_C, m) {
         py::arg("bn_z") = py::none(), py::arg("pad_w") = -1, py::arg("cfg") = -1,
         py::arg("bn_mask") = py::none(), py::arg("bn_y2") = py::none(),
         py::arg("bn_mean2") = py::none(), py::arg("bn_invstd2") = py::none(),
-        py::arg("wflip_pre") = py::none());
+        py::arg("wflip_pre") = py::none(), py::arg("generic_epi") = false);
+  // the fused-epilogue instantiation each launch of the last conv_dgrad call took, one per
+  // stride-parity class: "generic", or a compile-time feature set "Y" / "BITS_ADD" / "ADD"
+  m.def("dgrad_last_epi_sets", []() {
+    static const char* const kNames[] = {"generic", "Y", "BITS_ADD", "ADD"};
+    std::vector<std::string> out;
+    for (int v : mipipe::conv_dgrad_last_epi_sets()) out.push_back(kNames[v]);
+    return out;
+  });
   m.def("dgrad_preflip_ok", [](std::vector<int64_t> x_shape, std::vector<int64_t> w_shape,
                                int stride, int pad) {
     // whether conv_fwd(wflip=...) prepares this conv's data-grad weight (dgrad_preflip_ok)

@@ -209,13 +209,15 @@ template <class T, class C, bool BNIN>
 constexpr int bnin_lds_bytes() {
   return BNIN ? main_lds_bytes<T, C>() + kBnInMaxK * 8 : 0;
 }
+// SET: the data-grad epilogue's compile-time feature set (epilogue.hpp EpiSet; DGRAD_EPI only)
 template <class C, bool DENSE, bool ALIGNED, class T, bool DGRAD_EPI = false, bool SPLIT = false,
-          bool BNIN = false>
+          bool BNIN = false, int SET = kEpiSetGeneric>
 __global__ __launch_bounds__(C::THREADS, (conv_occ<T, C>())) void conv_fwd_kernel(
     const T* __restrict__ x, const T* __restrict__ w, ConvGeom g, uint32_t M,
     uint32_t tilesN, EpiParams e) {
   constexpr int BM = C::BM, BN = C::BN;
   static_assert(!BNIN || (DENSE && !C::PP && !SPLIT && !DGRAD_EPI), "folded-BN forward variant");
+  static_assert(SET == kEpiSetGeneric || (DGRAD_EPI && !SPLIT), "feature sets: unsplit data-grads");
   typedef typename std::conditional<
       BNIN, PolKCDenseBN<T>,
       typename std::conditional<DENSE, PolKCDense<T>, PolKCIm2col<ALIGNED, T>>::type>::type PA;
@@ -271,8 +273,8 @@ __global__ __launch_bounds__(C::THREADS, (conv_occ<T, C>())) void conv_fwd_kerne
   } else {
     // (a forward stores row m at row m; a forward-style data-grad class may remap its rows)
     constexpr int kOpt = kEpiNoAux | (DGRAD_EPI ? 0 : kEpiNoRemap | kEpiStatsEarly);
-    epilogue_out<BM, BN, DGRAD_EPI, T, C::WM, C::WN, false, C::PP, kOpt>(smem, acc, e, m0, n0, 0,
-                                                                         wave, lane);
+    epilogue_out<BM, BN, DGRAD_EPI, T, C::WM, C::WN, false, C::PP, kOpt, SET>(smem, acc, e, m0, n0,
+                                                                              0, wave, lane);
   }
 }
 
@@ -332,7 +334,7 @@ __global__ __launch_bounds__(C::THREADS) void conv_splitk_finish_kernel(
 }
 
 // TWO: BN-backward fusion of a two-branch block output (dense bf16 data-grads only)
-template <class C, bool DENSE, bool ALIGNED, class T, bool TWO = false>
+template <class C, bool DENSE, bool ALIGNED, class T, bool TWO = false, int SET = kEpiSetGeneric>
 __global__ __launch_bounds__(C::THREADS, (conv_occ<T, C>())) void conv_dgrad_kernel(
     const T* __restrict__ dy, const T* __restrict__ w, int Ho, int Wo, int Co, int taps,
     FastDiv fCo, DgradClass cls, uint32_t M, uint32_t tilesN, EpiParams e) {
@@ -358,8 +360,8 @@ __global__ __launch_bounds__(C::THREADS, (conv_occ<T, C>())) void conv_dgrad_ker
   };
   f32x4 acc[BM / C::WM / 16][BN / C::WN / 16];
   run_main_loop<T, C, PA, PB>(smem, ia, ib, m0, n0, 0, nk, acc, wave, lane);
-  epilogue_out<BM, BN, true, T, C::WM, C::WN, TWO, C::PP, kEpiNoAux>(smem, acc, e, m0, n0, 0, wave,
-                                                                     lane);
+  epilogue_out<BM, BN, true, T, C::WM, C::WN, TWO, C::PP, kEpiNoAux, SET>(smem, acc, e, m0, n0, 0,
+                                                                          wave, lane);
 }
 
 // ATOMIC: split-K partial tiles added with fp32 atomics; else the block owns its output tile

@@ -165,10 +165,46 @@ static void weight_flip(const T* w, T* wt, const ConvShape& s, const DgradClass&
                      s.KW, s.Ci, c.kh0, c.kw0, c.S, nkh, c.nkw);
 }
 
+// The fused epilogue's feature set (epilogue.hpp EpiSet) of a launch: exactly one of the three
+// combinations a ResNet bottleneck's backward runs, bf16, on a tile the training tuner can pick
+// for data-grads; everything else takes the run-time-generic epilogue.
+template <class T>
+static int pick_epi_set(const EpiParams& e, bool generic_epi) {
+  if (generic_epi || !std::is_same<T, __bf16>::value || e.bnr_y2 != nullptr) return kEpiSetGeneric;
+  const bool add = e.addend != nullptr, bnr = e.bnr_rep != nullptr;
+  const bool bits = e.bnr_mask != nullptr, z = e.bnr_z != nullptr;
+  if (add && !bnr) return kEpiSetAdd;
+  if (bnr && !add && !bits && !z) return kEpiSetY;
+  if (bnr && add && bits && !z) return kEpiSetBitsAdd;
+  return kEpiSetGeneric;
+}
+template <class C>
+constexpr bool kEpiSetTile = std::is_same<C, T0>::value || std::is_same<C, T1>::value ||
+                             std::is_same<C, T9>::value || std::is_same<C, T10>::value ||
+                             std::is_same<C, T14>::value;
+// the set each launch of the last conv_dgrad call took (one entry per stride-parity class)
+static std::vector<int> g_last_epi_sets;
+std::vector<int> conv_dgrad_last_epi_sets() { return g_last_epi_sets; }
+// f(integral_constant<int, SET>) with the set compiled for (C, T), else the generic one
+template <class C, class T, class F>
+static void with_epi_set(int set, F&& f) {
+  if constexpr (std::is_same<T, __bf16>::value && kEpiSetTile<C>) {
+    switch (set) {
+      case kEpiSetY: g_last_epi_sets.push_back(set); f(std::integral_constant<int, kEpiSetY>{}); return;
+      case kEpiSetBitsAdd: g_last_epi_sets.push_back(set); f(std::integral_constant<int, kEpiSetBitsAdd>{}); return;
+      case kEpiSetAdd: g_last_epi_sets.push_back(set); f(std::integral_constant<int, kEpiSetAdd>{}); return;
+      default: break;
+    }
+  }
+  g_last_epi_sets.push_back(kEpiSetGeneric);
+  f(std::integral_constant<int, kEpiSetGeneric>{});
+}
+
 template <class T>
 static void conv_dgrad_t(const void* dy, const void* w, void* dx, const ConvShape& s,
                          hipStream_t st, const DgradFusion* fz, int cfg_in, void* wflip,
-                         bool preflipped, float* split_ws) {
+                         bool preflipped, float* split_ws, bool generic_epi) {
+  g_last_epi_sets.clear();
   const bool dense = is_dense(s);
   long flip_off = 0;  // this class's slice of the flipped-weight workspace
   const bool aligned = s.Co % BK == 0;
@@ -201,6 +237,7 @@ static void conv_dgrad_t(const void* dy, const void* w, void* dx, const ConvShap
         e.rm_Hc = c.Hc; e.rm_Wc = c.Wc; e.rm_fHcWc = c.fHcWc; e.rm_fWc = c.fWc;
       }
       const int taps = s.KH * s.KW;
+      const int set = pick_epi_set<T>(e, generic_epi);
       const int cfg = resolve_dgrad_cfg(s, cfg_in, (long)c.ntaps * s.Co);
       if (wflip != nullptr && c.ntaps > 0 && e.bnr_y2 == nullptr) {
         // this class as a stride-1 forward convolution of dy (see conv_dgrad_fwd_style)
@@ -239,14 +276,21 @@ static void conv_dgrad_t(const void* dy, const void* w, void* dx, const ConvShap
               hipLaunchKernelGGL((conv_fwd_kernel<C, false, false, T, true, true>), g2d, block, 0, st, dyp, wt, g2, M, tN, es);
             hipLaunchKernelGGL((conv_splitk_finish_kernel<C, T, true>), dim3(tiles), block, 0, st,
                                (const float*)split_ws, SK, tN, e);
+            g_last_epi_sets.push_back(kEpiSetGeneric);
             return;
           }
-          if (dense2)
+          if (dense2) {
+            g_last_epi_sets.push_back(kEpiSetGeneric);
             hipLaunchKernelGGL((conv_fwd_kernel<C, true, false, T, true>), grid, block, 0, st, dyp, wt, g2, M, tN, e);
-          else if (aligned && (s.f32 || nkh * c.nkw <= 32))  // bf16: buffer im2col tap mask
-            hipLaunchKernelGGL((conv_fwd_kernel<C, false, true, T, true>), grid, block, 0, st, dyp, wt, g2, M, tN, e);
-          else
+          } else if (aligned && (s.f32 || nkh * c.nkw <= 32)) {  // bf16: buffer im2col tap mask
+            with_epi_set<C, T>(set, [&](auto st_tag) {
+              constexpr int SET = decltype(st_tag)::value;
+              hipLaunchKernelGGL((conv_fwd_kernel<C, false, true, T, true, false, false, SET>), grid, block, 0, st, dyp, wt, g2, M, tN, e);
+            });
+          } else {
+            g_last_epi_sets.push_back(kEpiSetGeneric);
             hipLaunchKernelGGL((conv_fwd_kernel<C, false, false, T, true>), grid, block, 0, st, dyp, wt, g2, M, tN, e);
+          }
         });
         return;
       }
@@ -259,21 +303,31 @@ static void conv_dgrad_t(const void* dy, const void* w, void* dx, const ConvShap
   // two-branch block output (host checks: dense, bf16)
           if constexpr (std::is_same<T, __bf16>::value)
             hipLaunchKernelGGL((conv_dgrad_kernel<C, true, false, T, true>), grid, block, 0, st, dyp, wp, s.Ho, s.Wo, s.Co, taps, fCo, c, M, tN, e);
-        } else if (dense)
-          hipLaunchKernelGGL((conv_dgrad_kernel<C, true, false, T>), grid, block, 0, st, dyp, wp, s.Ho, s.Wo, s.Co, taps, fCo, c, M, tN, e);
-        else if (aligned && (s.f32 || c.ntaps <= 32))  // bf16: buffer operands' tap mask
-          hipLaunchKernelGGL((conv_dgrad_kernel<C, false, true, T>), grid, block, 0, st, dyp, wp, s.Ho, s.Wo, s.Co, taps, fCo, c, M, tN, e);
-        else
+          g_last_epi_sets.push_back(kEpiSetGeneric);
+        } else if (dense) {
+          with_epi_set<C, T>(set, [&](auto st_tag) {
+            constexpr int SET = decltype(st_tag)::value;
+            hipLaunchKernelGGL((conv_dgrad_kernel<C, true, false, T, false, SET>), grid, block, 0, st, dyp, wp, s.Ho, s.Wo, s.Co, taps, fCo, c, M, tN, e);
+          });
+        } else if (aligned && (s.f32 || c.ntaps <= 32)) {  // bf16: buffer operands' tap mask
+          with_epi_set<C, T>(set, [&](auto st_tag) {
+            constexpr int SET = decltype(st_tag)::value;
+            hipLaunchKernelGGL((conv_dgrad_kernel<C, false, true, T, false, SET>), grid, block, 0, st, dyp, wp, s.Ho, s.Wo, s.Co, taps, fCo, c, M, tN, e);
+          });
+        } else {
+          g_last_epi_sets.push_back(kEpiSetGeneric);
           hipLaunchKernelGGL((conv_dgrad_kernel<C, false, false, T>), grid, block, 0, st, dyp, wp, s.Ho, s.Wo, s.Co, taps, fCo, c, M, tN, e);
+        }
       });
   });
 }
 
 void conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, hipStream_t st,
-                const DgradFusion* fz, int cfg, void* w_flip, bool preflipped, float* split_ws) {
+                const DgradFusion* fz, int cfg, void* w_flip, bool preflipped, float* split_ws,
+                bool generic_epi) {
   preflipped = preflipped && w_flip != nullptr && dgrad_preflip_ok(s);
-  if (s.f32) conv_dgrad_t<float>(dy, w, dx, s, st, fz, cfg, w_flip, preflipped, split_ws);
-  else conv_dgrad_t<__bf16>(dy, w, dx, s, st, fz, cfg, w_flip, preflipped, split_ws);
+  if (s.f32) conv_dgrad_t<float>(dy, w, dx, s, st, fz, cfg, w_flip, preflipped, split_ws, generic_epi);
+  else conv_dgrad_t<__bf16>(dy, w, dx, s, st, fz, cfg, w_flip, preflipped, split_ws, generic_epi);
 }
 
 }  // namespace mipipe

@@ -304,14 +304,36 @@ constexpr int kEpiLdsBytes() { return kStatsLdsOffset<BM, BN, T>() + 2 * WM * BN
 // memory latency per 16-B chunk.
 __device__ __attribute__((aligned(64))) uint4 g_epi_zero[4];
 
-template <int BM, int BN, bool FUSE, class T, int WM, int WN, bool TWO = false>
+// Compile-time feature sets of the fused data-grad epilogue (SET of EpiOps / epilogue_out; the
+// launcher picks one from the EpiParams it fills, conv_dgrad.hip).  A specialised set has no
+// loads, ring registers, unpacks or selects for the streams it lacks, and its ReLU mask source is
+// fixed; anything else runs kEpiSetGeneric, which selects at run time.
+constexpr int kEpiSetGeneric = 0;
+constexpr int kEpiSetY = 1;        // BN reduce, mask recomputed from y*scale + bias, no addend
+constexpr int kEpiSetBitsAdd = 2;  // BN reduce, mask from the 1-bit copy, addend
+constexpr int kEpiSetAdd = 3;      // addend only
+constexpr int kEpiSets = 4;
+template <int SET>
+struct EpiSet {
+  static constexpr bool kAny = SET != kEpiSetGeneric;
+  static constexpr bool kAdd = SET == kEpiSetBitsAdd || SET == kEpiSetAdd;
+  static constexpr bool kBnr = SET == kEpiSetY || SET == kEpiSetBitsAdd;
+  static constexpr bool kBits = SET == kEpiSetBitsAdd;
+};
+
+template <int BM, int BN, bool FUSE, class T, int WM, int WN, bool TWO = false,
+          int SET = kEpiSetGeneric>
 struct EpiOps {
   static constexpr int kThreads = 64 * WM * WN;
   static constexpr int CPR = BN / 8;  // 8-element chunks per row
   static constexpr int ITER = BM * CPR / kThreads;
   static constexpr int PF = FUSE ? (ITER < 4 ? ITER : 4) : 1;
-  Raw8<T> ad[PF], y[PF], z[PF], y2[TWO ? PF : 1];
-  uint32_t mk[PF];
+  typedef EpiSet<SET> Set;
+  static_assert(!Set::kAny || (FUSE && !TWO && std::is_same<T, __bf16>::value),
+                "specialised feature sets: fused bf16 one-branch epilogues");
+  Raw8<T> ad[!Set::kAny || Set::kAdd ? PF : 1], y[!Set::kAny || Set::kBnr ? PF : 1];
+  Raw8<T> z[Set::kAny ? 1 : PF], y2[TWO ? PF : 1];
+  uint32_t mk[!Set::kAny || Set::kBits ? PF : 1];
   // stream bases (the zero line when absent) and presence flags: wave-uniform
   const T *p_ad, *p_y, *p_z, *p_y2;
   const uint8_t* p_mk;
@@ -351,6 +373,23 @@ struct EpiOps {
 #pragma unroll
       for (int it = 0; it < PF; ++it) issue(e, m0, n0, it, it);
     }
+  }
+  // A specialised set: only its own streams, straight from EpiParams (clamped like issue()).
+  __device__ __forceinline__ void issue_set(const EpiParams& e, uint32_t m0, uint32_t n0, int it,
+                                            int slot) {
+    const uint32_t my_n = n0 + (threadIdx.x % CPR) * 8;
+    const uint32_t r = (threadIdx.x + it * kThreads) / CPR;
+    const uint32_t ld_n = my_n < e.N ? my_n : 0;
+    const uint32_t m = min(m0 + r, e.M - 1);
+    const long off = out_row(e, m) * e.ldc + ld_n;
+    const bool ntl = e.ntl != 0;
+    if constexpr (Set::kAdd) ad[slot] = ld_raw8(reinterpret_cast<const T*>(e.addend) + off, ntl);
+    if constexpr (Set::kBnr) y[slot] = ld_raw8(reinterpret_cast<const T*>(e.bnr_y) + off, ntl);
+    if constexpr (Set::kBits) mk[slot] = e.bnr_mask[off / 8];
+  }
+  __device__ __forceinline__ void prime_set(const EpiParams& e, uint32_t m0, uint32_t n0) {
+#pragma unroll
+    for (int it = 0; it < PF; ++it) issue_set(e, m0, n0, it, it);
   }
 };
 
@@ -474,15 +513,17 @@ constexpr int kEpiStatsEarly = 4;
 // FUSE: compile the dgrad fusions (addend / BN-backward reduction); kernels that never use
 // them keep their register budget.  early: an operand ring the kernel already primed.
 // TWO: the BN-backward fusion of a two-branch block output (e.bnr_y2 set, FUSE only).
+// SET: a compile-time feature set of the fused loop (EpiSet; bf16 data-grads) or the run-time
+// selects.
 // OPT: kEpiNoAux / kEpiNoRemap / kEpiStatsEarly.  The convolution kernels never store an aux
 // output, and a forward's rows are never remapped: their store loop then holds no GELU code (8 erf expansions
 // per 16-B chunk, in every unrolled iteration) and no per-row remap branch.
 template <int BM, int BN, bool FUSE = false, class T = __bf16, int WM = 2, int WN = 2,
-          bool TWO = false, bool HALVES = false, int OPT = 0>
+          bool TWO = false, bool HALVES = false, int OPT = 0, int SET = kEpiSetGeneric>
 __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16],
                              const EpiParams& e, uint32_t m0, uint32_t n0, uint32_t prow_base,
                              int wave, int lane,
-                             EpiOps<BM, BN, FUSE, T, WM, WN, TWO>* early = nullptr) {
+                             EpiOps<BM, BN, FUSE, T, WM, WN, TWO, SET>* early = nullptr) {
   constexpr int MT = BM / WM / 16, NT = BN / WN / 16;
   constexpr int kThreads = 64 * WM * WN;
   // BN-backward Σg·x̂ as invstd·(Σg·y - mean·Σg): exact products for bf16 g, y only; the fp32
@@ -500,15 +541,17 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
   constexpr int CPR = BN / 8;  // 8-element chunks per row
   constexpr int ITER = BM * CPR / kThreads;
   static_assert(kThreads % CPR == 0 && (BM * CPR) % kThreads == 0, "epilogue thread map");
-  const bool bnr = FUSE && e.bnr_rep != nullptr;
-  const bool has_add = FUSE && e.addend != nullptr;
-  const bool zmask = bnr && e.bnr_z != nullptr && e.bnr_mask == nullptr;
-  const bool bmask = bnr && e.bnr_mask != nullptr;
+  // (compile-time constants in a specialised set)
+  typedef EpiSet<SET> Set;
+  const bool bnr = Set::kAny ? Set::kBnr : FUSE && e.bnr_rep != nullptr;
+  const bool has_add = Set::kAny ? Set::kAdd : FUSE && e.addend != nullptr;
+  const bool zmask = !Set::kAny && bnr && e.bnr_z != nullptr && e.bnr_mask == nullptr;
+  const bool bmask = Set::kAny ? Set::kBits : bnr && e.bnr_mask != nullptr;
   const uint32_t my_cc = threadIdx.x % CPR, my_n = n0 + my_cc * 8;
   const uint32_t ld_n = my_n < e.N ? my_n : 0;
   // software-pipelined operand ring: PF iterations in flight; the first PF are issued now (unless
   // the kernel primed them before its main loop) so their latency overlaps the staging below
-  typedef EpiOps<BM, BN, FUSE, T, WM, WN, TWO> Ops;
+  typedef EpiOps<BM, BN, FUSE, T, WM, WN, TWO, SET> Ops;
   constexpr int PF = Ops::PF;
   Ops local;
   Ops& ops = early != nullptr ? *early : local;
@@ -542,8 +585,8 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
 #pragma unroll
     for (int q = 0; q < 8; ++q) sgx2[q] = 0.f;
   }
-  // bias / activation
-  if (e.bias != nullptr || e.act) {
+  // bias / activation (a specialised data-grad set has neither, nor forward statistics)
+  if (!Set::kAny && (e.bias != nullptr || e.act)) {
     // every bias quad loaded before use, at a clamped column (N % 4 == 0: a quad is all in or
     // all out; the zero line when there is no bias): loads behind per-element branches cost a
     // vmcnt(0) drain each (see EpiOps)
@@ -582,7 +625,7 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
   // wave-instructions, no per-block partial rows to reduce later.  (bf16 outputs: stats_mfma
   // after the staging below instead.)
   constexpr bool MSTATS = kMfmaStats && std::is_same<T, __bf16>::value;
-  if (!MSTATS && e.st_sum != nullptr) {
+  if (!Set::kAny && !MSTATS && e.st_sum != nullptr) {
     float* lst = reinterpret_cast<float*>(smem + kStatsLdsOffset<BM, BN, T>());  // [2][WM][BN]
     // every column's shift requested before any is used (clamped column: unconditional loads),
     // so the block waits one memory latency here, not one per 16-column group
@@ -653,13 +696,63 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
         *reinterpret_cast<uint2*>(smem + ml * P + nl * 2) = v;
       }
     }
+  const bool fused = FUSE && (has_add || bnr);
+  T* C = reinterpret_cast<T*>(e.C);
+  float sg[8], sgx[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) sg[q] = sgx[q] = 0.f;
+  if constexpr (Set::kAny) {
+    // A specialised set: the generic fused loop below with the absent streams and the mask
+    // select taken out.  The arithmetic on each element and the order of every sum are the
+    // generic loop's.  (A second copy of the loop for tiles wholly inside M x N, without row
+    // weights, store predicates and address clamps, measured no gain:
+    // profiles/dgrad_epilogue_items.txt.)
+    static_assert(kBnrUncentered || !Set::kBnr, "specialised sets: uncentred bf16 sums");
+    ops.prime_set(e, m0, n0);  // accumulators are dead now
+    lds_barrier();
+    {
+#pragma unroll
+      for (int it = 0; it < ITER; ++it) {
+        const int c = threadIdx.x + it * kThreads;
+        const uint32_t r = c / CPR, cc = c % CPR;
+        const uint32_t m = m0 + r, n = n0 + cc * 8;
+        const uint4 v = *reinterpret_cast<const uint4*>(smem + r * P + cc * 16);
+        float f[8];
+        unpack8(v, f);
+        if constexpr (Set::kAdd) {
+          float a[8];
+          unpack_raw(ops.ad[it % PF], a);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) f[q] += a[q];
+        }
+        const bool ok = m < e.M && n < e.N;
+        if constexpr (Set::kBnr) {
+          float yv[8];
+          unpack_raw(ops.y[it % PF], yv);
+          const uint32_t bits = Set::kBits ? ops.mk[it % PF] : 0u;
+          const float w = ok ? 1.f : 0.f;  // rows past M add nothing to the sums
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const bool on = Set::kBits ? ((bits >> q) & 1u) != 0u
+                                       : yv[q] * b_sc[q] + b_bi[q] > 0.f;
+            const float gq = on ? as_stored<T>(f[q]) : 0.f;  // stats of the stored g
+            f[q] = gq;
+            const float gw = w * gq;
+            sg[q] += gw;
+            sgx[q] = fmaf(gw, yv[q], sgx[q]);
+          }
+        }
+        if (ok) store8(C + out_row(e, m) * e.ldc + n, f, e.nt != 0);
+        if (it + PF < ITER) ops.issue_set(e, m0, n0, it + PF, it % PF);
+      }
+    }
+  } else {
   if (early == nullptr) ops.prime(e, m0, n0);  // accumulators are dead now
   lds_barrier();
   // The MFMA statistics only read the staged tile, so the output stores need not wait for them:
   // with kEpiStatsEarly (plain store loop: nothing overwrites the tile after it) they run after
   // the stores are issued.  Elsewhere (the fused loop's column sums reuse the tile's LDS) they
   // stay in front.
-  const bool fused = FUSE && (has_add || bnr);
   if (MSTATS && e.st_sum != nullptr) {
     if constexpr (!SEARLY) {
       stats_shift_load<BN, NWV>(e, n0, wave, lane, st_sh);
@@ -685,10 +778,6 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
       }
     }
   }
-  T* C = reinterpret_cast<T*>(e.C);
-  float sg[8], sgx[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) sg[q] = sgx[q] = 0.f;
   if (fused) {
     // fused loop: the ring's next loads are issued unconditionally (absent streams read the
     // zero line), so hipcc keeps PF iterations of loads in flight with counted waits
@@ -780,6 +869,7 @@ __device__ void epilogue_out(char* smem, f32x4 (&acc)[BM / WM / 16][BN / WN / 16
       if (e.st_sum != nullptr) stats_mfma<BM, BN, NWV, true>(smem, e, m0, n0, wave, lane, st_sh);
     }
   }
+  }  // !Set::kAny
   if (FUSE && bnr) {
     if constexpr (kBnrUncentered) {
       // this thread's columns: Σg·x̂ = invstd·(Σg·y - mean·Σg) (linear: the sums below add these)

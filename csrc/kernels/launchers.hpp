@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 #include "plan.hpp"
 
@@ -185,7 +186,11 @@ struct DgradFusion {
 // forward-style classes only; the other data-grad kernels ignore the split)
 void conv_dgrad(const void* dy, const void* w, void* dx, const ConvShape& s, hipStream_t st,
                 const DgradFusion* fz = nullptr, int cfg = -1, void* w_flip = nullptr,
-                bool preflipped = false, float* split_ws = nullptr);
+                bool preflipped = false, float* split_ws = nullptr, bool generic_epi = false);
+// The fused epilogue has compile-time feature sets (epilogue.hpp EpiSet: 1 = Y, 2 = BITS_ADD,
+// 3 = ADD) beside its run-time-generic code (0); generic_epi forces the latter.  The set each
+// launch of the last conv_dgrad call took, in launch order (one per stride-parity class).
+std::vector<int> conv_dgrad_last_epi_sets();
 bool conv_dgrad_fwd_style(const ConvShape& s, bool dense_too);
 int conv_dgrad_tiles_m(const ConvShape& s, int cfg);  // M-tiles over all stride classes
 // dw is ACCUMULATED into (split-K fp32 atomics, or a plain read-modify-write when unsplit): pass
