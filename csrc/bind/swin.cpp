@@ -1,0 +1,113 @@
+// Swin Transformer entries of mipipe._C (kernels/winattn.hip): shifted-window attention forward
+// and backward, and the PatchMerging permutation with its inverse.
+#include "bind/common.hpp"
+
+namespace mipipe_bind {
+namespace {
+
+inline void check_aligned16(const Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must start on a 16-byte boundary");
+}
+
+// t [B*Hs*Ws, mult*heads*32] bf16 of a window-attention call
+void check_win(const Tensor& t, const char* name, int64_t B, int64_t Hs, int64_t Ws,
+               int64_t heads, int64_t mult, int64_t sy, int64_t sx) {
+  check_bf16(t, name);
+  TORCH_CHECK(B >= 1 && heads >= 1 && Hs >= 1 && Ws >= 1 && t.numel() > 0,
+              "window_attention: empty input");
+  TORCH_CHECK(Hs % 7 == 0 && Ws % 7 == 0, "window_attention: the map ", Hs, "x", Ws,
+              " is not a whole number of 7x7 windows");
+  TORCH_CHECK((sy == 0 || sy == 3) && (sx == 0 || sx == 3),
+              "window_attention: the shift must be 0 or 3 per axis, got (", sy, ", ", sx, ")");
+  TORCH_CHECK(B * Hs * Ws * 3 * heads * 32 < (1ll << 31),
+              "window_attention: qkv must have fewer than 2^31 elements");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == B * Hs * Ws && t.size(1) == mult * heads * 32, name,
+              " must be [", B * Hs * Ws, ", ", mult * heads * 32, "] (head width 32), got ",
+              t.sizes());
+  check_aligned16(t, name);
+}
+
+const float* check_table(const Tensor& table, const Tensor& like, int64_t heads) {
+  check_vec(table, 169 * heads, "table");
+  TORCH_CHECK(table.device() == like.device(), "table must be on qkv's device");
+  return table.data_ptr<float>();
+}
+
+Tensor winattn_fwd(Tensor qkv, Tensor table, int64_t B, int64_t Hs, int64_t Ws, int64_t heads,
+                   int64_t sy, int64_t sx) {
+  check_win(qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
+  const float* tp = check_table(table, qkv, heads);
+  c10::DeviceGuard g(qkv.device());
+  auto o = torch::empty({qkv.size(0), heads * 32}, qkv.options());
+  mipipe::winattn_fwd(qkv.data_ptr(), tp, o.data_ptr(), (int)B, (int)Hs, (int)Ws, (int)heads,
+                      (int)sy, (int)sx, stream());
+  return o;
+}
+
+// -> (dqkv, dtable); the table gradient is ACCUMULATED into dtable_acc (fp32 [169*heads], e.g.
+// the flat-gradient view) and returned as None, or into a new zeroed buffer when none is given
+std::tuple<Tensor, optional<Tensor>> winattn_bwd(Tensor dout, Tensor qkv, Tensor table, int64_t B,
+                                                 int64_t Hs, int64_t Ws, int64_t heads, int64_t sy,
+                                                 int64_t sx, optional<Tensor> dtable_acc) {
+  check_win(qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
+  check_win(dout, "dout", B, Hs, Ws, heads, 1, sy, sx);
+  TORCH_CHECK(dout.device() == qkv.device(), "dout must be on qkv's device");
+  const float* tp = check_table(table, qkv, heads);
+  c10::DeviceGuard g(qkv.device());
+  auto fo = qkv.options().dtype(at::kFloat);
+  optional<Tensor> dtable;
+  float* dt;
+  if (dtable_acc.has_value()) {
+    dt = fptr(dtable_acc, 169 * heads);
+    TORCH_CHECK(dtable_acc->device() == qkv.device(), "the accumulator must be on qkv's device");
+  } else {
+    dtable = torch::zeros({169, heads}, fo);
+    dt = dtable->data_ptr<float>();
+  }
+  auto dqkv = torch::empty_like(qkv);
+  auto partial = torch::empty({(int64_t)mipipe::winattn_runs(B * (Hs / 7) * (Ws / 7)),
+                               169 * heads}, fo);
+  mipipe::winattn_bwd(dout.data_ptr(), qkv.data_ptr(), tp, dqkv.data_ptr(),
+                      partial.data_ptr<float>(), dt, (int)B, (int)Hs, (int)Ws, (int)heads, (int)sy,
+                      (int)sx, stream());
+  return {dqkv, dtable};
+}
+
+// x [B*Hs*Ws, C] (or any shape with that many elements) -> [B*Hs/2*Ws/2, 4C]; bwd: the inverse
+Tensor patch_merge(Tensor t, int64_t B, int64_t Hs, int64_t Ws, bool bwd) {
+  check_bf16(t, bwd ? "dy" : "x");
+  TORCH_CHECK(B >= 1 && Hs >= 1 && Ws >= 1 && t.numel() > 0, "patch_merge: empty input");
+  TORCH_CHECK(Hs % 2 == 0 && Ws % 2 == 0, "patch_merge: the map ", Hs, "x", Ws,
+              " must have even sides");
+  TORCH_CHECK(t.numel() % (B * Hs * Ws) == 0, "patch_merge: ", t.numel(),
+              " elements are not [", B, ", ", Hs, ", ", Ws, ", C]");
+  const int64_t C = t.numel() / (B * Hs * Ws);
+  TORCH_CHECK(C % 8 == 0, "patch_merge: C must be a multiple of 8, got ", C);
+  TORCH_CHECK(t.numel() < (1ll << 31), "patch_merge: fewer than 2^31 elements are supported");
+  check_aligned16(t, bwd ? "dy" : "x");
+  c10::DeviceGuard g(t.device());
+  auto out = bwd ? torch::empty({B * Hs * Ws, C}, t.options())
+                 : torch::empty({B * (Hs / 2) * (Ws / 2), 4 * C}, t.options());
+  mipipe::patch_merge(t.data_ptr(), out.data_ptr(), (int)B, (int)Hs, (int)Ws, (int)C, bwd,
+                      stream());
+  return out;
+}
+
+}  // namespace
+
+void bind_swin(py::module& m) {
+  m.def("winattn_fwd", &winattn_fwd, py::arg("qkv"), py::arg("table"), py::arg("batch"),
+        py::arg("hs"), py::arg("ws"), py::arg("heads"), py::arg("shift_y"), py::arg("shift_x"));
+  m.def("winattn_bwd", &winattn_bwd, py::arg("dout"), py::arg("qkv"), py::arg("table"),
+        py::arg("batch"), py::arg("hs"), py::arg("ws"), py::arg("heads"), py::arg("shift_y"),
+        py::arg("shift_x"), py::arg("dtable") = py::none());
+  m.def("patch_merge", &patch_merge, py::arg("x"), py::arg("batch"), py::arg("hs"), py::arg("ws"),
+        py::arg("bwd") = false);
+  // launch geometry, for the tests' edge shapes
+  m.attr("WIN_WAVES") = mipipe::kWinWaves;
+  m.attr("WIN_RUN") = mipipe::kWinRun;
+  m.attr("WIN_MAX_RUNS") = mipipe::kWinMaxRuns;
+}
+
+}  // namespace mipipe_bind

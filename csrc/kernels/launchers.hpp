@@ -488,6 +488,29 @@ void tokens_assemble_fwd(const void* e, const float* cls, const float* pos, void
 // (ascending b, one owner per element: the same bits in every run)
 void tokens_assemble_bwd(const void* dh, void* de, float* dpos, float* dcls, int B, int N, int D,
                          bool f32, hipStream_t st);
+// ---- Swin (winattn.hip) ---------------------------------------------------------------------
+// Shifted-window attention, head width 32, 7x7 windows, bf16: qkv [B*Hs*Ws][3*H*32] (q | k | v,
+// head-major, NHWC token order), o [B*Hs*Ws][H*32], table fp32 [169][H] (the master
+// relative_position_bias_table); sy, sx in {0, 3}: the cyclic shift per axis; Hs % 7 == Ws % 7
+// == 0.  A block = kWinWaves waves of one head, one (window, head) per wave at a time, walking
+// groups of kWinRun windows; at most kWinMaxRuns group slots per head (grid-strided beyond), each
+// with one partial row of the bias-table gradient.
+constexpr int kWinWaves = 4;
+constexpr int kWinRun = 8;
+constexpr int kWinMaxRuns = 256;
+int winattn_runs(long nwin);  // group slots (= partial rows) of a launch over nwin windows
+void winattn_fwd(const void* qkv, const float* table, void* o, int B, int Hs, int Ws, int H,
+                 int sy, int sx, hipStream_t st);
+// dqkv like qkv (every element written); dtable [169][H] += the bias-table gradient, summed in a
+// fixed order through partial [winattn_runs][169*H] (scratch): no float atomics in any mode
+void winattn_bwd(const void* dout, const void* qkv, const float* table, void* dqkv,
+                 float* partial, float* dtable, int B, int Hs, int Ws, int H, int sy, int sx,
+                 hipStream_t st);
+// PatchMerging's gather: x [B, Hs, Ws, C] -> out [B*Hs/2*Ws/2, 4C], column groups (0::2, 0::2),
+// (1::2, 0::2), (0::2, 1::2), (1::2, 1::2); bwd: the inverse permutation (in = dy, out = dx).
+// bf16, C % 8 == 0, even Hs and Ws.
+void patch_merge(const void* in, void* out, int B, int Hs, int Ws, int C, bool bwd,
+                 hipStream_t st);
 // *correct += #rows whose first maximal logit is at the label (torch.argmax tie rule)
 void top1_correct(const void* logits, const int64_t* labels, int R, int V, int* correct,
                   hipStream_t st, bool f32 = false);

@@ -1,0 +1,488 @@
+// Swin's shifted-window attention for gfx950: head width 32, 7x7 windows, forward + backward,
+// and the PatchMerging permutation.
+//
+// Layout (the packed-projection convention of attention.hip, rows in NHWC token order):
+//   qkv [B*Hs*Ws][3*H*32] bf16 (q | k | v, head-major), o [B*Hs*Ws][H*32] bf16, dqkv like qkv,
+//   table [169][H] fp32: the master relative_position_bias_table, read as it stands.
+// Per (window, head): P = softmax(q·kᵀ·scale + table[rel(i,j)] + mask(i,j)), o = P·v with
+// rel(i,j) = (yi-yj+6)*13 + (xi-xj+6) and mask = -100 between tokens of different shift regions.
+// The token at (wy*7+y, wx*7+x) of the SHIFTED map is row ((wy*7+y+sy) mod Hs, (wx*7+x+sx) mod Ws)
+// of qkv / o / dqkv: roll, window partition, reverse and un-roll are address arithmetic only.
+//
+// Design: one wave owns one (window, head) at a time; a whole window-head is 49 x 32 (padded to
+// 64 x 32 inside the tile), so scores, softmax, P·V and the full backward live in one wave's
+// registers: no online softmax, no lse, no K/V streaming, no dQ atomics.  A block = kWinWaves
+// waves of ONE head walking groups of kWinRun windows (grid-strided past kWinMaxRuns groups).
+// Per block, once: the head's bias expanded to E[query][key] (log2 domain; dead rows / columns
+// -inf, so padding drops out of every sum as an exact zero) in LDS.
+//
+//   forward   Xᵀ = K·Qᵀ on mfma_f32_32x32x16_bf16 (2x2 tiles x 2 k-steps), K / Q fragments loaded
+//             straight from global memory into the operand registers (16-byte loads, no LDS); a
+//             lane owns a query column, so max / sum are in-lane + one cross-half exchange.
+//             Oᵀ = Vᵀ·P with the bf16-converted accumulator as the B operand and Vᵀ read from a
+//             per-wave LDS image by ds_read_b64_tr_b16.
+//   backward  phase A (lane = query): recompute Pᵀ, dPᵀ = V·dOᵀ, δ = Σ_k P∘dP (= rowsum(dO∘O),
+//             from fp32 values, O is not read), dSᵀ = P∘(dP-δ), dQᵀ = Kᵀ·dSᵀ; the per-query
+//             (max, 1/sum, δ) go to LDS.  Phase B (lane = key): the same two products with the
+//             operands swapped give P and dS with a key per lane (the statistics come from LDS,
+//             so no cross-lane reduction), then dVᵀ = dOᵀ·P and dKᵀ = Qᵀ·dS.  Every product uses
+//             "accumulator as the next B operand"; Kᵀ, Qᵀ, dOᵀ come from LDS images by
+//             transposed reads.  dqkv is stored at the same rolled addresses.
+//   dtable    a lane's accumulator registers hold the same (i, j) for every window: the wave
+//             sums dSᵀ over its windows in fp32 registers; at the end the block's waves add their
+//             sums in wave order into one 49 x 49 LDS tile, 169 threads add their diagonal's
+//             entries in index order into the partial row of (group slot, head), and
+//             det_sum_rows adds the partial rows in order into the gradient (+=).  No float
+//             atomics: the same bits on every launch in every mode.
+#include "common.hpp"
+#include "launchers.hpp"
+
+namespace mipipe {
+namespace winattn {
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+
+constexpr int D = 32;       // head width
+constexpr int WS = 7;       // window side
+constexpr int NT = WS * WS;  // tokens per window (padded to 64 in the tiles)
+constexpr int NREL = (2 * WS - 1) * (2 * WS - 1);
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kMaskLog2 = -100.f * kLog2e;
+constexpr int kPitch = 80;            // bytes per row of a [64][32] bf16 LDS image (16-B aligned)
+constexpr int kImg = 64 * kPitch;
+constexpr int kEP = 65;               // floats per row of E (conflict-free along both axes)
+constexpr int kERows = NT + 1;        // 49 query rows + one all -inf row for the dead queries
+constexpr int kEBytes = (kERows * kEP * 4 + 15) / 16 * 16;
+
+__device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 zero16() {
+  f32x16 z;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) z[i] = 0.f;
+  return z;
+}
+// reg i of a 32x32 accumulator <-> row (i&3) + 8(i>>2) + 4h (h = lane >> 5), column lane & 31
+__device__ __forceinline__ int acc_row(int i, int hl) { return (i & 3) + 8 * (i >> 2) + 4 * hl; }
+// regs 8s..8s+7 of an accumulator as the B operand of the next product (k = its rows)
+__device__ __forceinline__ bf16x8 pack_acc(const f32x16& x, int s) {
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (__bf16)x[8 * s + j];
+  return v;
+}
+// A operand holding Tᵀ of a row-major [64][32] image T, k (row) order of pack_acc: element j of
+// lane half h <-> row r0 + 8(j>>2) + 4h + (j&3); the lane's column is lane & 31.
+__device__ __forceinline__ bf16x8 ld_tr(const char* img, uint32_t r0, int lane) {
+  const uint32_t hl = lane >> 5, li = lane & 15, q = li >> 2, p = li & 3;
+  const char* a0 = img + (r0 + 4 * hl + q) * kPitch + (16 * ((lane >> 4) & 1) + 4 * p) * 2;
+  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
+  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) s16x4*)(a0 + 8 * kPitch));
+  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8, v);
+}
+// this wave's LDS accesses so far have completed; nothing moves across (wave-private images)
+__device__ __forceinline__ void wave_lds_fence() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+struct Args {
+  const __bf16* qkv;
+  const __bf16* dout;   // backward
+  __bf16* o;            // forward
+  __bf16* dqkv;         // backward
+  const float* table;   // [169][H]
+  float* partial;       // backward: [nruns][169 * H]
+  int Hs, Ws, H, sy, sx, nwy, nwx;
+  int nwin;             // B * nwy * nwx
+  int nruns;            // group slots = gridDim.x / H
+  float scale, scale_log2;
+};
+
+// E[min(q, 49)][k] = table[rel(q, k)][h] * log2e for live (q, k), -inf for dead ones
+__device__ __forceinline__ void fill_bias(float* E, const Args& a, int h, int tid, int nthr) {
+  for (int idx = tid; idx < kERows * 64; idx += nthr) {
+    const int q = idx >> 6, k = idx & 63;
+    float v = -INFINITY;
+    if (q < NT && k < NT) {
+      const int rel = (q / WS - k / WS + WS - 1) * (2 * WS - 1) + (q % WS - k % WS + WS - 1);
+      v = a.table[(long)rel * a.H + h] * kLog2e;
+    }
+    E[q * kEP + k] = v;
+  }
+}
+
+// The lane's part of the region mask, the same bits in both orientations (the relation is
+// symmetric): bit 16*t + i of my / mx <-> tokens n = 32*tile + (lane & 31) and 32*t +
+// acc_row(i, hl) lie on different sides of the axis' shift boundary (7 - shift).
+__device__ __forceinline__ void lane_masks(int tile, int lane, int sy, int sx, uint32_t& my,
+                                           uint32_t& mx) {
+  const int n = min(32 * tile + (lane & 31), NT - 1), hl = lane >> 5;
+  const bool ny = n / WS < WS - sy, nx = n % WS < WS - sx;
+  my = mx = 0;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int m = min(32 * t + acc_row(i, hl), NT - 1);
+      my |= (uint32_t)((m / WS < WS - sy) != ny) << (16 * t + i);
+      mx |= (uint32_t)((m % WS < WS - sx) != nx) << (16 * t + i);
+    }
+}
+
+struct Win {
+  long row[2];      // qkv / o row of token 32*t + (lane & 31) (clamped to the window's last token)
+  bool lasty, lastx;  // the window touches the wrapped border of a shifted axis
+};
+__device__ __forceinline__ Win window(const Args& a, int w, int lane) {
+  const int wx = w % a.nwx, t = w / a.nwx, wy = t % a.nwy, b = t / a.nwy;
+  Win g;
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt) {
+    const int n = min(32 * tt + (lane & 31), NT - 1);
+    int gy = wy * WS + n / WS + a.sy, gx = wx * WS + n % WS + a.sx;
+    gy -= gy >= a.Hs ? a.Hs : 0;
+    gx -= gx >= a.Ws ? a.Ws : 0;
+    g.row[tt] = ((long)b * a.Hs + gy) * a.Ws + gx;
+  }
+  g.lasty = a.sy != 0 && wy == a.nwy - 1;
+  g.lastx = a.sx != 0 && wx == a.nwx - 1;
+  return g;
+}
+
+// the two 16-byte k-steps of token rows' head slice as MFMA operands (row = lane & 31)
+__device__ __forceinline__ void ld_frags(const __bf16* base, const Win& g, long ld, int hl,
+                                         bf16x8 (&f)[2][2]) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+      f[t][st] = *reinterpret_cast<const bf16x8*>(base + g.row[t] * ld + 16 * st + 8 * hl);
+}
+__device__ __forceinline__ void st_image(char* img, const bf16x8 (&f)[2][2], int lane) {
+  const int r = lane & 31, hl = lane >> 5;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+      *reinterpret_cast<bf16x8*>(img + (32 * t + r) * kPitch + (16 * st + 8 * hl) * 2) = f[t][st];
+}
+
+// Lane = query n = 32*qt + r: p[sub][i] = softmax over keys 32*sub + acc_row(i, hl), normalised;
+// mu / inv_l the column's max (0 for a dead query) and 1 / sum (0 for a dead query).
+__device__ __forceinline__ void probs_by_query(const bf16x8 (&kf)[2][2], const bf16x8 (&qf)[2],
+                                               const float* Eq, uint32_t mbits, float scale_log2,
+                                               int hl, f32x16 (&p)[2], float& mu, float& inv_l) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int sub = 0; sub < 2; ++sub) {
+    p[sub] = mfma32(kf[sub][1], qf[1], mfma32(kf[sub][0], qf[0], zero16()));
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float v = p[sub][i] * scale_log2 + Eq[32 * sub + acc_row(i, hl)];
+      v += (mbits >> (16 * sub + i)) & 1u ? kMaskLog2 : 0.f;
+      p[sub][i] = v;
+      m = fmaxf(m, v);
+    }
+  }
+  m = fmaxf(m, __shfl_xor(m, 32));
+  mu = m == -INFINITY ? 0.f : m;
+  float l = 0.f;
+#pragma unroll
+  for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      p[sub][i] = exp2f(p[sub][i] - mu);
+      l += p[sub][i];
+    }
+  l += __shfl_xor(l, 32);
+  inv_l = l > 0.f ? 1.f / l : 0.f;
+#pragma unroll
+  for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) p[sub][i] *= inv_l;
+}
+
+// accumulator (lane = token column, regs = d rows) -> 8-byte pieces of the token's head slice
+__device__ __forceinline__ void st_cols(__bf16* dst, const f32x16& x, float s, int hl) {
+#pragma unroll
+  for (int ig = 0; ig < 4; ++ig)
+    *reinterpret_cast<uint2*>(dst + 8 * ig + 4 * hl) =
+        make_uint2(pack2(x[4 * ig] * s, x[4 * ig + 1] * s),
+                   pack2(x[4 * ig + 2] * s, x[4 * ig + 3] * s));
+}
+
+__global__ __launch_bounds__(64 * kWinWaves) void winattn_fwd_kernel(Args a) {
+  __shared__ __attribute__((aligned(16))) char smem[kEBytes + kWinWaves * kImg];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, hl = lane >> 5, r = lane & 31;
+  const int h = blockIdx.x % a.H, run = blockIdx.x / a.H;
+  float* E = reinterpret_cast<float*>(smem);
+  char* vimg = smem + kEBytes + wave * kImg;
+  fill_bias(E, a, h, tid, 64 * kWinWaves);
+  uint32_t my[2], mx[2];
+  lane_masks(0, lane, a.sy, a.sx, my[0], mx[0]);
+  lane_masks(1, lane, a.sy, a.sx, my[1], mx[1]);
+  __syncthreads();
+  const long ld = 3l * a.H * D, ldo = (long)a.H * D;
+  const __bf16* qb = a.qkv + h * D;
+  const int ngroups = (a.nwin + kWinRun - 1) / kWinRun;
+  for (int grp = run; grp < ngroups; grp += a.nruns)
+    for (int w = grp * kWinRun + wave; w < min((grp + 1) * kWinRun, a.nwin); w += kWinWaves) {
+      const Win g = window(a, w, lane);
+      bf16x8 qf[2][2], kf[2][2], vf[2][2];
+      ld_frags(qb, g, ld, hl, qf);
+      ld_frags(qb + ldo, g, ld, hl, kf);
+      ld_frags(qb + 2 * ldo, g, ld, hl, vf);
+      wave_lds_fence();  // the previous window's transposed reads are done
+      st_image(vimg, vf, lane);
+      wave_lds_fence();
+      bf16x8 vt[2][2];
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) vt[sub][ks] = ld_tr(vimg, 32 * sub + 16 * ks, lane);
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        const int qn = 32 * qt + r;
+        const uint32_t mb = (g.lasty ? my[qt] : 0u) | (g.lastx ? mx[qt] : 0u);
+        f32x16 p[2];
+        float mu, inv_l;
+        probs_by_query(kf, qf[qt], E + min(qn, NT) * kEP, mb, a.scale_log2, hl, p, mu, inv_l);
+        f32x16 o = zero16();
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) o = mfma32(vt[sub][ks], pack_acc(p[sub], ks), o);
+        if (qn < NT) st_cols(a.o + g.row[qt] * ldo + h * D, o, 1.f, hl);
+      }
+    }
+}
+
+// LDS per wave: image X (K, then dO) | image Y (Q) | per-query max, 1/sum, δ
+constexpr int kBwdWave = 2 * kImg + 3 * 64 * 4;
+
+__global__ __launch_bounds__(64 * kWinWaves) void winattn_bwd_kernel(Args a) {
+  __shared__ __attribute__((aligned(16))) char smem[kEBytes + kWinWaves * kBwdWave];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, hl = lane >> 5, r = lane & 31;
+  const int h = blockIdx.x % a.H, run = blockIdx.x / a.H;
+  float* E = reinterpret_cast<float*>(smem);
+  char* ximg = smem + kEBytes + wave * kBwdWave;
+  char* yimg = ximg + kImg;
+  float* stat = reinterpret_cast<float*>(yimg + kImg);  // [3][64]
+  fill_bias(E, a, h, tid, 64 * kWinWaves);
+  uint32_t my[2], mx[2];
+  lane_masks(0, lane, a.sy, a.sx, my[0], mx[0]);
+  lane_masks(1, lane, a.sy, a.sx, my[1], mx[1]);
+  __syncthreads();
+  const long ld = 3l * a.H * D, ldo = (long)a.H * D;
+  const __bf16* qb = a.qkv + h * D;
+  f32x16 dsum[2][2];  // Σ over this wave's windows of dSᵀ: [query tile][key tile]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) dsum[i >> 1][i & 1] = zero16();
+  const int ngroups = (a.nwin + kWinRun - 1) / kWinRun;
+  for (int grp = run; grp < ngroups; grp += a.nruns)
+    for (int w = grp * kWinRun + wave; w < min((grp + 1) * kWinRun, a.nwin); w += kWinWaves) {
+      const Win g = window(a, w, lane);
+      bf16x8 qf[2][2], kf[2][2], vf[2][2], df[2][2];
+      ld_frags(qb, g, ld, hl, qf);
+      ld_frags(qb + ldo, g, ld, hl, kf);
+      ld_frags(qb + 2 * ldo, g, ld, hl, vf);
+      ld_frags(a.dout + h * D, g, ldo, hl, df);
+      wave_lds_fence();
+      st_image(ximg, kf, lane);
+      st_image(yimg, qf, lane);
+      wave_lds_fence();
+      // ---- phase A: lane = query
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        __builtin_amdgcn_sched_barrier(0);
+        const int qn = 32 * qt + r;
+        const uint32_t mb = (g.lasty ? my[qt] : 0u) | (g.lastx ? mx[qt] : 0u);
+        f32x16 p[2];
+        float mu, inv_l;
+        probs_by_query(kf, qf[qt], E + min(qn, NT) * kEP, mb, a.scale_log2, hl, p, mu, inv_l);
+        f32x16 dp[2];
+        float delta = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+          dp[sub] = mfma32(vf[sub][1], df[qt][1], mfma32(vf[sub][0], df[qt][0], zero16()));
+#pragma unroll
+          for (int i = 0; i < 16; ++i) delta += p[sub][i] * dp[sub][i];
+        }
+        delta += __shfl_xor(delta, 32);
+        f32x16 dq = zero16();
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            p[sub][i] *= dp[sub][i] - delta;  // dSᵀ; exactly 0 for dead queries and keys (p = 0)
+            dsum[qt][sub][i] += p[sub][i];
+          }
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks)
+            dq = mfma32(ld_tr(ximg, 32 * sub + 16 * ks, lane), pack_acc(p[sub], ks), dq);
+        }
+        if (qn < NT) st_cols(a.dqkv + g.row[qt] * ld + h * D, dq, a.scale, hl);
+        if (hl == 0) {
+          stat[qn] = mu;
+          stat[64 + qn] = inv_l;
+          stat[128 + qn] = delta;
+        }
+      }
+      wave_lds_fence();  // phase A's reads of the K image are done, the statistics are written
+      st_image(ximg, df, lane);
+      wave_lds_fence();
+      // ---- phase B: lane = key
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+        __builtin_amdgcn_sched_barrier(0);
+        const int kn = 32 * kt + r;
+        const uint32_t mb = (g.lasty ? my[kt] : 0u) | (g.lastx ? mx[kt] : 0u);
+        f32x16 dv = zero16(), dk = zero16();
+#pragma unroll
+        for (int qs = 0; qs < 2; ++qs) {
+          __builtin_amdgcn_sched_barrier(0);
+          f32x16 p = mfma32(qf[qs][1], kf[kt][1], mfma32(qf[qs][0], kf[kt][0], zero16()));
+          f32x16 ds = mfma32(df[qs][1], vf[kt][1], mfma32(df[qs][0], vf[kt][0], zero16()));
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int qn = 32 * qs + acc_row(i, hl);
+            float v = p[i] * a.scale_log2 + E[min(qn, NT) * kEP + kn];
+            v += (mb >> (16 * qs + i)) & 1u ? kMaskLog2 : 0.f;
+            p[i] = exp2f(v - stat[qn]) * stat[64 + qn];
+            ds[i] = p[i] * (ds[i] - stat[128 + qn]);
+          }
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            dv = mfma32(ld_tr(ximg, 32 * qs + 16 * ks, lane), pack_acc(p, ks), dv);
+            dk = mfma32(ld_tr(yimg, 32 * qs + 16 * ks, lane), pack_acc(ds, ks), dk);
+          }
+        }
+        if (kn < NT) {
+          __bf16* dst = a.dqkv + g.row[kt] * ld + ldo + h * D;
+          st_cols(dst, dk, a.scale, hl);
+          st_cols(dst + ldo, dv, 1.f, hl);
+        }
+      }
+    }
+  // ---- bias-table gradient: the waves' sums added in wave order into E (reused), then one
+  // thread per table entry adds its diagonal's (query, key) pairs in index order
+  for (int wv = 0; wv < kWinWaves; ++wv) {
+    __syncthreads();
+    if (wave != wv) continue;
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int qn = 32 * qt + r, kn = 32 * sub + acc_row(i, hl);
+          if (qn < NT) {
+            float* e = E + qn * kEP + kn;
+            *e = wv == 0 ? dsum[qt][sub][i] : *e + dsum[qt][sub][i];
+          }
+        }
+  }
+  __syncthreads();
+  if (tid < NREL) {
+    const int dy = tid / (2 * WS - 1) - (WS - 1), dx = tid % (2 * WS - 1) - (WS - 1);
+    float acc = 0.f;
+    for (int yq = max(0, dy); yq <= min(WS - 1, WS - 1 + dy); ++yq)
+      for (int xq = max(0, dx); xq <= min(WS - 1, WS - 1 + dx); ++xq)
+        acc += E[(yq * WS + xq) * kEP + (yq - dy) * WS + (xq - dx)];
+    a.partial[(long)run * NREL * a.H + (long)tid * a.H + h] = acc;
+  }
+}
+
+// ------------------------------------------------------------------------------ patch_merge
+// One item = 8 channels.  Forward: output item o of row (b, i, j), column group g, channels c8
+// <- x[b, 2i + (g & 1), 2j + (g >> 1), c8].  Backward: dx item of (b, y, x, c8) <- dy row
+// (b, y / 2, x / 2), group (y & 1) + 2 (x & 1).  Stores in output order, one owner per element.
+template <bool BWD>
+__global__ __launch_bounds__(256) void patch_merge_kernel(const uint4* __restrict__ in,
+                                                          uint4* __restrict__ out, uint32_t items,
+                                                          FastDiv fC8, FastDiv fW, FastDiv fH,
+                                                          uint32_t Ws) {
+  for (uint32_t o = blockIdx.x * 256 + threadIdx.x; o < items; o += gridDim.x * 256) {
+    uint32_t t = fC8.div(o);
+    const uint32_t c8 = o - t * fC8.d;
+    uint32_t src;
+    if (BWD) {  // fW = Ws, fH = Hs: o indexes dx
+      const uint32_t u = fW.div(t), x = t - u * fW.d;
+      const uint32_t b = fH.div(u), y = u - b * fH.d;
+      const uint32_t row = (b * (fH.d >> 1) + (y >> 1)) * (Ws >> 1) + (x >> 1);
+      src = (row * 4 + (y & 1) + 2 * (x & 1)) * fC8.d + c8;
+    } else {  // fW = Ws / 2, fH = Hs / 2: o indexes the merged rows
+      const uint32_t g = t & 3;
+      t >>= 2;
+      const uint32_t u = fW.div(t), j = t - u * fW.d;
+      const uint32_t b = fH.div(u), i = u - b * fH.d;
+      src = ((b * (2 * fH.d) + 2 * i + (g & 1)) * Ws + 2 * j + (g >> 1)) * fC8.d + c8;
+    }
+    out[o] = in[src];
+  }
+}
+
+}  // namespace winattn
+
+int winattn_runs(long nwin) {
+  const long groups = (nwin + kWinRun - 1) / kWinRun;
+  return (int)std::max<long>(1, std::min<long>(groups, kWinMaxRuns));
+}
+
+static winattn::Args winattn_args(const void* qkv, const float* table, int B, int Hs, int Ws,
+                                  int H, int sy, int sx) {
+  winattn::Args a{};
+  a.qkv = (const __bf16*)qkv;
+  a.table = table;
+  a.Hs = Hs; a.Ws = Ws; a.H = H; a.sy = sy; a.sx = sx;
+  a.nwy = Hs / winattn::WS;
+  a.nwx = Ws / winattn::WS;
+  a.nwin = B * a.nwy * a.nwx;
+  a.nruns = winattn_runs(a.nwin);
+  a.scale = 0.17677669529663687f;  // 32^-1/2
+  a.scale_log2 = a.scale * winattn::kLog2e;
+  return a;
+}
+
+void winattn_fwd(const void* qkv, const float* table, void* o, int B, int Hs, int Ws, int H,
+                 int sy, int sx, hipStream_t st) {
+  winattn::Args a = winattn_args(qkv, table, B, Hs, Ws, H, sy, sx);
+  a.o = (__bf16*)o;
+  hipLaunchKernelGGL(winattn::winattn_fwd_kernel, dim3(a.nruns * H), dim3(64 * kWinWaves), 0, st,
+                     a);
+}
+
+void winattn_bwd(const void* dout, const void* qkv, const float* table, void* dqkv,
+                 float* partial, float* dtable, int B, int Hs, int Ws, int H, int sy, int sx,
+                 hipStream_t st) {
+  winattn::Args a = winattn_args(qkv, table, B, Hs, Ws, H, sy, sx);
+  a.dout = (const __bf16*)dout;
+  a.dqkv = (__bf16*)dqkv;
+  a.partial = partial;
+  hipLaunchKernelGGL(winattn::winattn_bwd_kernel, dim3(a.nruns * H), dim3(64 * kWinWaves), 0, st,
+                     a);
+  det_sum_rows(partial, nullptr, a.nruns, winattn::NREL * H, dtable, nullptr, true, st);
+}
+
+void patch_merge(const void* in, void* out, int B, int Hs, int Ws, int C, bool bwd,
+                 hipStream_t st) {
+  const long n = (long)B * Hs * Ws * C;
+  if (n <= 0) return;
+  const uint32_t items = (uint32_t)(n / 8);
+  const FastDiv fC8((uint32_t)C / 8);
+  const int grid = grid1d(items, 1, 4096);
+  if (bwd)
+    hipLaunchKernelGGL(winattn::patch_merge_kernel<true>, dim3(grid), dim3(256), 0, st,
+                       (const uint4*)in, (uint4*)out, items, fC8, FastDiv((uint32_t)Ws),
+                       FastDiv((uint32_t)Hs), (uint32_t)Ws);
+  else
+    hipLaunchKernelGGL(winattn::patch_merge_kernel<false>, dim3(grid), dim3(256), 0, st,
+                       (const uint4*)in, (uint4*)out, items, fC8, FastDiv((uint32_t)Ws / 2),
+                       FastDiv((uint32_t)Hs / 2), (uint32_t)Ws);
+}
+
+}  // namespace mipipe

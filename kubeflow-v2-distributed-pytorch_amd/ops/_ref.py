@@ -521,6 +521,103 @@ def tokens_assemble_bwd(dh: Tensor, batch: int) -> Tuple[Tensor, Tensor, Tensor]
     return g[:, 1:].reshape(-1, D).contiguous(), dpos.reshape(-1), dpos[0].clone()
 
 
+# ---- Swin: shifted-window attention and PatchMerging (csrc/kernels/winattn.hip)
+WIN = 7        # window side
+WIN_HEAD = 32  # head width
+
+
+def _shift2(shift) -> Tuple[int, int]:
+    return (int(shift), int(shift)) if isinstance(shift, int) else (int(shift[0]), int(shift[1]))
+
+
+def window_geometry(Hs: int, Ws: int, shift, device="cpu"):
+    """(idx [nW, 49], rel [49, 49], mask [nW, 49, 49] bool) of a 7x7 window partition of the map
+    rolled by ``-shift``: ``idx[w, n]`` is the row (inside a sample, NHWC order) of token n of
+    window w — the token at (wy*7+y, wx*7+x) of the shifted map is ((wy*7+y+sy) % Hs,
+    (wx*7+x+sx) % Ws) of the unshifted one; ``rel[i, j] = (yi-yj+6)*13 + (xi-xj+6)`` indexes the
+    bias table; ``mask`` is True where the two tokens lie in different ones of the 3x3 shift
+    regions (torchvision's ``shifted_window_attention``; an axis with shift 0 has one region)."""
+    sy, sx = _shift2(shift)
+    if Hs % WIN or Ws % WIN or Hs < WIN or Ws < WIN:
+        raise ValueError(f"the map {Hs}x{Ws} is not a whole number of {WIN}x{WIN} windows")
+    if sy not in (0, 3) or sx not in (0, 3):
+        raise ValueError(f"the shift must be 0 or 3 per axis, got ({sy}, {sx})")
+    Y, X = torch.arange(Hs, device=device), torch.arange(Ws, device=device)
+
+    def part(t):  # [Hs, Ws] of the shifted map -> [nW, 49]
+        return t.reshape(Hs // WIN, WIN, Ws // WIN, WIN).permute(0, 2, 1, 3).reshape(-1, WIN * WIN)
+
+    idx = part(((Y + sy) % Hs)[:, None] * Ws + ((X + sx) % Ws)[None, :])
+    ry = (Y >= Hs - WIN).long() + (Y >= Hs - sy).long() if sy else torch.zeros_like(Y)
+    rx = (X >= Ws - WIN).long() + (X >= Ws - sx).long() if sx else torch.zeros_like(X)
+    reg = part(ry[:, None] * 3 + rx[None, :])
+    n = torch.arange(WIN * WIN, device=device)
+    y, x = n // WIN, n % WIN
+    rel = (y[:, None] - y[None, :] + WIN - 1) * (2 * WIN - 1) + (x[:, None] - x[None, :] + WIN - 1)
+    return idx, rel, reg[:, :, None] != reg[:, None, :]
+
+
+def window_attention(qkv: Tensor, table: Tensor, B: int, Hs: int, Ws: int, heads: int, shift,
+                     do: Optional[Tensor] = None):
+    """Swin's window attention on the packed projection: qkv [B*Hs*Ws, 3*heads*32] (q | k | v,
+    head-major, NHWC token order), table [169, heads] -> o [B*Hs*Ws, heads*32]; per window and
+    head ``P = softmax(q kᵀ 32^-½ + table[rel] + (-100 across shift regions))``, ``o = P v``.
+    With ``do`` also the closed-form backward: returns (o, dqkv, dtable) with ``δ = rowsum(dO∘O)``,
+    ``dS = P∘(dO Vᵀ - δ)``, ``dtable[rel] = Σ dS``.  fp32 (fp64 for fp64 input)."""
+    idx, rel, msk = window_geometry(Hs, Ws, shift, qkv.device)
+    nW, N, D = idx.shape[0], WIN * WIN, WIN_HEAD
+    if qkv.shape != (B * Hs * Ws, 3 * heads * D):
+        raise ValueError(f"qkv must be [{B * Hs * Ws}, {3 * heads * D}], got {tuple(qkv.shape)}")
+    tab = _f(table).reshape(-1, heads)
+    x = _f(qkv).reshape(B, Hs * Ws, 3, heads, D)[:, idx]  # [B, nW, 49, 3, h, D]
+    q, k, v = (x[:, :, :, i].transpose(2, 3) for i in range(3))  # [B, nW, h, 49, D]
+    scale = D ** -0.5
+    s = q @ k.transpose(-1, -2) * scale + tab[rel].permute(2, 0, 1)
+    s = s + (msk.to(s.dtype) * -100.0)[None, :, None]
+    p = torch.softmax(s, -1)
+    o = p @ v
+
+    def rows(t, out):  # [B, nW, h, 49, D] -> its tokens' rows of out [B, Hs*Ws, h, D]
+        out[:, idx.reshape(-1)] = t.transpose(2, 3).reshape(B, nW * N, heads, D)
+        return out
+
+    of = rows(o, torch.empty(B, Hs * Ws, heads, D, dtype=o.dtype, device=o.device))
+    of = of.reshape(B * Hs * Ws, heads * D).to(qkv.dtype)
+    if do is None:
+        return of
+    dof = _f(do).reshape(B, Hs * Ws, heads, D)[:, idx].transpose(2, 3)
+    dv = p.transpose(-1, -2) @ dof
+    dp = dof @ v.transpose(-1, -2)
+    ds = p * (dp - (dof * o).sum(-1, keepdim=True))
+    dq, dk = ds @ k * scale, ds.transpose(-1, -2) @ q * scale
+    dqkv = torch.empty(B, Hs * Ws, 3, heads, D, dtype=o.dtype, device=o.device)
+    for i, t in enumerate((dq, dk, dv)):
+        rows(t, dqkv[:, :, i])
+    dtable = torch.zeros_like(tab).index_add_(
+        0, rel.reshape(-1), ds.sum((0, 1)).permute(1, 2, 0).reshape(N * N, heads))
+    return of, dqkv.reshape(B * Hs * Ws, 3 * heads * D).to(qkv.dtype), dtable
+
+
+def patch_merge(x: Tensor, B: int, Hs: int, Ws: int) -> Tensor:
+    """x [B, Hs, Ws, C] (any shape with those elements) -> [B*Hs/2*Ws/2, 4C]: torchvision's
+    PatchMerging gather, column groups (0::2, 0::2), (1::2, 0::2), (0::2, 1::2), (1::2, 1::2)."""
+    if Hs % 2 or Ws % 2:
+        raise ValueError(f"patch_merge: the map {Hs}x{Ws} must have even sides")
+    x = x.reshape(B, Hs, Ws, -1)
+    parts = [x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]]
+    return torch.cat(parts, -1).reshape(-1, 4 * x.shape[-1])
+
+
+def patch_merge_bwd(dy: Tensor, B: int, Hs: int, Ws: int) -> Tensor:
+    """The inverse permutation of :func:`patch_merge`: dy [B*Hs/2*Ws/2, 4C] -> dx [B*Hs*Ws, C]."""
+    C = dy.shape[-1] // 4
+    g = dy.reshape(B, Hs // 2, Ws // 2, 4, C)
+    dx = torch.empty(B, Hs, Ws, C, dtype=dy.dtype, device=dy.device)
+    dx[:, 0::2, 0::2], dx[:, 1::2, 0::2] = g[:, :, :, 0], g[:, :, :, 1]
+    dx[:, 0::2, 1::2], dx[:, 1::2, 1::2] = g[:, :, :, 2], g[:, :, :, 3]
+    return dx.reshape(B * Hs * Ws, C)
+
+
 _M32 = 0xFFFFFFFF
 
 

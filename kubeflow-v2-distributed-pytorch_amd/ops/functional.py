@@ -1578,6 +1578,59 @@ def attention(qkv: Tensor, batch: int, seq: int, heads: int, mask: Optional[Tens
                               float(p_drop), seed)
 
 
+class _WindowAttentionFn(Function):
+    @staticmethod
+    def forward(ctx, qkv, table, B, Hs, Ws, heads, shift):
+        ctx.save_for_backward(qkv)
+        ctx.table, ctx.cfg = table, (B, Hs, Ws, heads, shift)
+        return K.window_attention_fwd(qkv, table.detach(), B, Hs, Ws, heads, shift)
+
+    @staticmethod
+    def backward(ctx, do):
+        (qkv,) = ctx.saved_tensors
+        table = ctx.table
+        do = do.contiguous()
+        tt = _direct_grad_target(table) if K.use_native(do) and ctx.needs_input_grad[1] else None
+        dqkv, dt = K.window_attention_bwd(do, qkv, table.detach(), *ctx.cfg,
+                                          dtable=None if tt is None else tt[1].reshape(-1))
+        if tt is not None:
+            tt[0].grad_ready(table)
+        elif dt is not None:
+            dt = dt.reshape(table.shape).to(table.dtype) if ctx.needs_input_grad[1] else None
+        return dqkv, dt, None, None, None, None, None
+
+
+def window_attention(qkv: Tensor, table: Tensor, batch: int, hs: int, ws: int, heads: int,
+                     shift=0) -> Tensor:
+    """Swin's (shifted-)window attention over the packed QKV projection output, one kernel each
+    way: qkv [B*Hs*Ws, 3*heads*32] (rows in NHWC token order; q | k | v, head-major), ``table`` the
+    fp32 ``relative_position_bias_table`` parameter [169, heads], ``shift`` 0 or 3 (or a (y, x)
+    pair: an axis with a single window takes 0) -> o [B*Hs*Ws, heads*32].  The cyclic shift, the
+    window partition and their inverses are address arithmetic inside the kernels; the backward
+    recomputes the probabilities and sums the table's gradient in a fixed order, straight into the
+    flat gradient buffer when the parameter lives in one."""
+    return _WindowAttentionFn.apply(qkv.contiguous(), table, int(batch), int(hs), int(ws),
+                                    int(heads), shift)
+
+
+class _PatchMergeFn(Function):
+    @staticmethod
+    def forward(ctx, x, B, Hs, Ws):
+        ctx.cfg, ctx.shape = (B, Hs, Ws), x.shape
+        return K.patch_merge(x, B, Hs, Ws)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx = K.patch_merge(dy.contiguous(), *ctx.cfg, bwd=True)
+        return dx.reshape(ctx.shape), None, None, None
+
+
+def patch_merge(x: Tensor, batch: int, hs: int, ws: int) -> Tensor:
+    """Swin's PatchMerging gather: x [B*Hs*Ws, C] (NHWC rows) -> [B*Hs/2*Ws/2, 4C] with the column
+    groups in torchvision's order; the backward is the inverse permutation."""
+    return _PatchMergeFn.apply(x.contiguous(), int(batch), int(hs), int(ws))
+
+
 class _DropoutFn(Function):
     @staticmethod
     def forward(ctx, x, p, seed):

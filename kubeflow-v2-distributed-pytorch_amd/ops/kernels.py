@@ -30,7 +30,7 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "dwconv7_fwd", "dwconv7_dgrad", "dwconv7_wgrad", "drop_path_keep",
            "scale_residual_fwd", "scale_residual_bwd",
            "bn_act_pool_fwd", "bn_act_pool_bwd_reduce", "bn_act_pool_bwd_apply", "se_scale_fwd",
-           "se_scale_bwd"]
+           "se_scale_bwd", "window_attention_fwd", "window_attention_bwd", "patch_merge"]
 
 _ALLOW_REF_ON_GPU = os.environ.get("MIPIPE_ALLOW_REF_ON_GPU", "0") == "1"
 
@@ -574,6 +574,42 @@ def tokens_assemble_bwd(dh, batch, dpos_acc=None, dcls_acc=None):
         dcls_acc.add_(dcls.to(dcls_acc.dtype))
         return de, None, None
     return de, dpos, dcls
+
+
+# ----------------------------------------------------------------------------- winattn.hip
+def window_attention_fwd(qkv, table, B, Hs, Ws, heads, shift):
+    """Swin's shifted-window attention (7x7 windows, head width 32): qkv [B*Hs*Ws, 3*heads*32]
+    (q | k | v, head-major, NHWC token order), ``table`` fp32 [169, heads] (the master
+    relative_position_bias_table), ``shift`` 0 / 3 or a (y, x) pair -> o [B*Hs*Ws, heads*32]
+    (:func:`_ref.window_attention`).  Native: bf16."""
+    sy, sx = _ref._shift2(shift)
+    if use_native(qkv):
+        return native().winattn_fwd(qkv, table.reshape(-1), int(B), int(Hs), int(Ws), int(heads),
+                                    sy, sx)
+    return _ref.window_attention(qkv, table, B, Hs, Ws, heads, (sy, sx))
+
+
+def window_attention_bwd(do, qkv, table, B, Hs, Ws, heads, shift, dtable=None):
+    """-> (dqkv, dtable): the table gradient [169, heads] fp32 is ACCUMULATED into ``dtable`` (a
+    flat-gradient view; returned as None) when given.  Native: P is recomputed in the kernel, the
+    table gradient is summed in a fixed order — the same bits on every launch, in every mode."""
+    sy, sx = _ref._shift2(shift)
+    if use_native(do):
+        return native().winattn_bwd(do, qkv, table.reshape(-1), int(B), int(Hs), int(Ws),
+                                    int(heads), sy, sx, dtable)
+    _, dqkv, g = _ref.window_attention(qkv, table, B, Hs, Ws, heads, (sy, sx), do)
+    if dtable is not None:
+        dtable.add_(g.reshape(dtable.shape).to(dtable.dtype))
+        g = None
+    return dqkv, g
+
+
+def patch_merge(x, B, Hs, Ws, bwd=False):
+    """PatchMerging's gather x [B, Hs, Ws, C] -> [B*Hs/2*Ws/2, 4C] (:func:`_ref.patch_merge`), or
+    with ``bwd`` its inverse permutation on the gradient.  Native: bf16, C % 8 == 0."""
+    if use_native(x):
+        return native().patch_merge(x, int(B), int(Hs), int(Ws), bool(bwd))
+    return _ref.patch_merge_bwd(x, B, Hs, Ws) if bwd else _ref.patch_merge(x, B, Hs, Ws)
 
 
 def colsum(x, out=None):

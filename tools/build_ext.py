@@ -34,6 +34,11 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 
 
+# kernel files compiled without the packed fp32 VALU forms (v_pk_add / mul / fma_f32)
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+_NO_PACKED_FP32_FILES = {"winattn.hip"}
+
+
 def _newest_header() -> float:
     hs = glob.glob(os.path.join(CSRC, "**", "*.hpp"), recursive=True) + \
         glob.glob(os.path.join(CSRC, "**", "*.h"), recursive=True)
@@ -125,7 +130,9 @@ def build_kernels(jobs: int = 8, force: bool = False, verbose: bool = True) -> s
     hdr = _newest_header()
     jobs_list = []
     for s in srcs:
-        jobs_list.append((s, os.path.join(BUILD, "C", os.path.basename(s) + ".o"), hip_flags))
+        extra = _NO_PACKED_FP32 if os.path.basename(s) in _NO_PACKED_FP32_FILES else []
+        jobs_list.append((s, os.path.join(BUILD, "C", os.path.basename(s) + ".o"),
+                          hip_flags + extra))
     for s in cpps:
         jobs_list.append((s, os.path.join(BUILD, "C", os.path.basename(s) + ".o"), cpp_flags))
     msgs = []
