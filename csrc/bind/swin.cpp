@@ -1,5 +1,6 @@
-// Swin Transformer entries of mipipe._C (kernels/winattn.hip): shifted-window attention forward
-// and backward, and the PatchMerging permutation with its inverse.
+// Swin Transformer entries of mipipe._C (kernels/winattn.hip, winattn8.hip): shifted-window
+// attention forward and backward (V1: 7x7 windows, V2: 8x8 windows with cosine scores), and the
+// PatchMerging permutation with its inverse.
 #include "bind/common.hpp"
 
 namespace mipipe_bind {
@@ -74,6 +75,83 @@ std::tuple<Tensor, optional<Tensor>> winattn_bwd(Tensor dout, Tensor qkv, Tensor
   return {dqkv, dtable};
 }
 
+// ---- Swin V2 (winattn8.hip): 8x8 windows, cosine scores
+void check_win8(const Tensor& t, const char* name, int64_t B, int64_t Hs, int64_t Ws,
+                int64_t heads, int64_t mult, int64_t sy, int64_t sx) {
+  check_bf16(t, name);
+  TORCH_CHECK(B >= 1 && heads >= 1 && Hs >= 1 && Ws >= 1 && t.numel() > 0,
+              "window_attention_v2: empty input");
+  TORCH_CHECK(Hs % 8 == 0 && Ws % 8 == 0, "window_attention_v2: the map ", Hs, "x", Ws,
+              " is not a whole number of 8x8 windows");
+  TORCH_CHECK((sy == 0 || sy == 4) && (sx == 0 || sx == 4),
+              "window_attention_v2: the shift must be 0 or 4 per axis, got (", sy, ", ", sx, ")");
+  TORCH_CHECK(B * Hs * Ws * 3 * heads * 32 < (1ll << 31),
+              "window_attention_v2: qkv must have fewer than 2^31 elements");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == B * Hs * Ws && t.size(1) == mult * heads * 32, name,
+              " must be [", B * Hs * Ws, ", ", mult * heads * 32, "] (head width 32), got ",
+              t.sizes());
+  check_aligned16(t, name);
+}
+
+// bias fp32 [225, heads], logit_scale fp32 [heads] on qkv's device
+void check_win8_params(const Tensor& bias, const Tensor& logit_scale, const Tensor& like,
+                       int64_t heads) {
+  check_f32(bias, "bias");
+  check_f32(logit_scale, "logit_scale");
+  TORCH_CHECK(bias.dim() == 2 && bias.size(0) == 225 && bias.size(1) == heads,
+              "bias must be [225, ", heads, "], got ", bias.sizes());
+  TORCH_CHECK(logit_scale.dim() == 1 && logit_scale.size(0) == heads, "logit_scale must be [",
+              heads, "], got ", logit_scale.sizes());
+  TORCH_CHECK(bias.device() == like.device() && logit_scale.device() == like.device(),
+              "bias and logit_scale must be on qkv's device");
+}
+
+Tensor winattn8_fwd(Tensor qkv, Tensor bias, Tensor logit_scale, int64_t B, int64_t Hs,
+                    int64_t Ws, int64_t heads, int64_t sy, int64_t sx) {
+  check_win8(qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
+  check_win8_params(bias, logit_scale, qkv, heads);
+  c10::DeviceGuard g(qkv.device());
+  auto o = torch::empty({qkv.size(0), heads * 32}, qkv.options());
+  mipipe::winattn8_fwd(qkv.data_ptr(), bias.data_ptr<float>(), logit_scale.data_ptr<float>(),
+                       o.data_ptr(), (int)B, (int)Hs, (int)Ws, (int)heads, (int)sy, (int)sx,
+                       stream());
+  return o;
+}
+
+// -> (dqkv, dbias, dlogit_scale); each of the two parameter gradients is ACCUMULATED into its
+// accumulator (fp32 [225*heads] / [heads], e.g. a flat-gradient view) and returned as None, or
+// into a new zeroed buffer when none is given
+std::tuple<Tensor, optional<Tensor>, optional<Tensor>> winattn8_bwd(
+    Tensor dout, Tensor qkv, Tensor bias, Tensor logit_scale, int64_t B, int64_t Hs, int64_t Ws,
+    int64_t heads, int64_t sy, int64_t sx, optional<Tensor> dbias_acc,
+    optional<Tensor> dlogit_acc) {
+  check_win8(qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
+  check_win8(dout, "dout", B, Hs, Ws, heads, 1, sy, sx);
+  TORCH_CHECK(dout.device() == qkv.device(), "dout must be on qkv's device");
+  check_win8_params(bias, logit_scale, qkv, heads);
+  c10::DeviceGuard g(qkv.device());
+  auto fo = qkv.options().dtype(at::kFloat);
+  optional<Tensor> dbias, dlogit;
+  auto target = [&](const optional<Tensor>& acc, optional<Tensor>& fresh, at::IntArrayRef shape,
+                    int64_t n) {
+    if (acc.has_value()) {
+      TORCH_CHECK(acc->device() == qkv.device(), "the accumulator must be on qkv's device");
+      return fptr(acc, n);
+    }
+    fresh = torch::zeros(shape, fo);
+    return fresh->data_ptr<float>();
+  };
+  float* db = target(dbias_acc, dbias, {225, heads}, 225 * heads);
+  float* dl = target(dlogit_acc, dlogit, {heads}, heads);
+  auto dqkv = torch::empty_like(qkv);
+  auto partial = torch::empty({(int64_t)mipipe::winattn8_runs(B * (Hs / 8) * (Ws / 8)),
+                               226 * heads}, fo);
+  mipipe::winattn8_bwd(dout.data_ptr(), qkv.data_ptr(), bias.data_ptr<float>(),
+                       logit_scale.data_ptr<float>(), dqkv.data_ptr(), partial.data_ptr<float>(),
+                       db, dl, (int)B, (int)Hs, (int)Ws, (int)heads, (int)sy, (int)sx, stream());
+  return {dqkv, dbias, dlogit};
+}
+
 // x [B*Hs*Ws, C] (or any shape with that many elements) -> [B*Hs/2*Ws/2, 4C]; bwd: the inverse
 Tensor patch_merge(Tensor t, int64_t B, int64_t Hs, int64_t Ws, bool bwd) {
   check_bf16(t, bwd ? "dy" : "x");
@@ -104,10 +182,20 @@ void bind_swin(py::module& m) {
         py::arg("shift_x"), py::arg("dtable") = py::none());
   m.def("patch_merge", &patch_merge, py::arg("x"), py::arg("batch"), py::arg("hs"), py::arg("ws"),
         py::arg("bwd") = false);
+  m.def("winattn8_fwd", &winattn8_fwd, py::arg("qkv"), py::arg("bias"), py::arg("logit_scale"),
+        py::arg("batch"), py::arg("hs"), py::arg("ws"), py::arg("heads"), py::arg("shift_y"),
+        py::arg("shift_x"));
+  m.def("winattn8_bwd", &winattn8_bwd, py::arg("dout"), py::arg("qkv"), py::arg("bias"),
+        py::arg("logit_scale"), py::arg("batch"), py::arg("hs"), py::arg("ws"), py::arg("heads"),
+        py::arg("shift_y"), py::arg("shift_x"), py::arg("dbias") = py::none(),
+        py::arg("dlogit_scale") = py::none());
   // launch geometry, for the tests' edge shapes
   m.attr("WIN_WAVES") = mipipe::kWinWaves;
   m.attr("WIN_RUN") = mipipe::kWinRun;
   m.attr("WIN_MAX_RUNS") = mipipe::kWinMaxRuns;
+  m.attr("WIN8_WAVES") = mipipe::kWin8Waves;
+  m.attr("WIN8_RUN") = mipipe::kWin8Run;
+  m.attr("WIN8_MAX_RUNS") = mipipe::kWin8MaxRuns;
 }
 
 }  // namespace mipipe_bind

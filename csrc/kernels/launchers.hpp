@@ -506,6 +506,23 @@ void winattn_fwd(const void* qkv, const float* table, void* o, int B, int Hs, in
 void winattn_bwd(const void* dout, const void* qkv, const float* table, void* dqkv,
                  float* partial, float* dtable, int B, int Hs, int Ws, int H, int sy, int sx,
                  hipStream_t st);
+// ---- Swin V2 (winattn8.hip) -----------------------------------------------------------------
+// Shifted-window cosine attention, head width 32, 8x8 windows, bf16: qkv / o as above, bias fp32
+// [225][H] (the finished continuous-position bias), logit_scale fp32 [H] (the master parameter:
+// the kernel clamps at ln 100 and exponentiates); sy, sx in {0, 4}; Hs % 8 == Ws % 8 == 0.  The
+// same block / group / slot scheme as above, with constants of its own.
+constexpr int kWin8Waves = 4;
+constexpr int kWin8Run = 8;
+constexpr int kWin8MaxRuns = 256;
+int winattn8_runs(long nwin);  // group slots of a launch over nwin windows
+void winattn8_fwd(const void* qkv, const float* bias, const float* logit_scale, void* o, int B,
+                  int Hs, int Ws, int H, int sy, int sx, hipStream_t st);
+// dqkv like qkv (every element written); dbias [225][H] and dlogit_scale [H] += their gradients,
+// summed in a fixed order through partial [winattn8_runs][(225 + 1)*H] (scratch; the 225*H-wide
+// bias rows first, then the H-wide logit_scale rows): no float atomics in any mode
+void winattn8_bwd(const void* dout, const void* qkv, const float* bias, const float* logit_scale,
+                  void* dqkv, float* partial, float* dbias, float* dlogit_scale, int B, int Hs,
+                  int Ws, int H, int sy, int sx, hipStream_t st);
 // PatchMerging's gather: x [B, Hs, Ws, C] -> out [B*Hs/2*Ws/2, 4C], column groups (0::2, 0::2),
 // (1::2, 0::2), (0::2, 1::2), (1::2, 1::2); bwd: the inverse permutation (in = dy, out = dx).
 // bf16, C % 8 == 0, even Hs and Ws.

@@ -36,12 +36,12 @@
 //             atomics: the same bits on every launch in every mode.
 #include "common.hpp"
 #include "launchers.hpp"
+#include "wintile.hpp"
 
 namespace mipipe {
 namespace winattn {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
+using namespace wintile;
 
 constexpr int D = 32;       // head width
 constexpr int WS = 7;       // window side
@@ -49,45 +49,9 @@ constexpr int NT = WS * WS;  // tokens per window (padded to 64 in the tiles)
 constexpr int NREL = (2 * WS - 1) * (2 * WS - 1);
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kMaskLog2 = -100.f * kLog2e;
-constexpr int kPitch = 80;            // bytes per row of a [64][32] bf16 LDS image (16-B aligned)
-constexpr int kImg = 64 * kPitch;
 constexpr int kEP = 65;               // floats per row of E (conflict-free along both axes)
 constexpr int kERows = NT + 1;        // 49 query rows + one all -inf row for the dead queries
 constexpr int kEBytes = (kERows * kEP * 4 + 15) / 16 * 16;
-
-__device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-// reg i of a 32x32 accumulator <-> row (i&3) + 8(i>>2) + 4h (h = lane >> 5), column lane & 31
-__device__ __forceinline__ int acc_row(int i, int hl) { return (i & 3) + 8 * (i >> 2) + 4 * hl; }
-// regs 8s..8s+7 of an accumulator as the B operand of the next product (k = its rows)
-__device__ __forceinline__ bf16x8 pack_acc(const f32x16& x, int s) {
-  bf16x8 v;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = (__bf16)x[8 * s + j];
-  return v;
-}
-// A operand holding Tᵀ of a row-major [64][32] image T, k (row) order of pack_acc: element j of
-// lane half h <-> row r0 + 8(j>>2) + 4h + (j&3); the lane's column is lane & 31.
-__device__ __forceinline__ bf16x8 ld_tr(const char* img, uint32_t r0, int lane) {
-  const uint32_t hl = lane >> 5, li = lane & 15, q = li >> 2, p = li & 3;
-  const char* a0 = img + (r0 + 4 * hl + q) * kPitch + (16 * ((lane >> 4) & 1) + 4 * p) * 2;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(a0 + 8 * kPitch));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-// this wave's LDS accesses so far have completed; nothing moves across (wave-private images)
-__device__ __forceinline__ void wave_lds_fence() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
 
 struct Args {
   const __bf16* qkv;
@@ -162,15 +126,6 @@ __device__ __forceinline__ void ld_frags(const __bf16* base, const Win& g, long 
     for (int st = 0; st < 2; ++st)
       f[t][st] = *reinterpret_cast<const bf16x8*>(base + g.row[t] * ld + 16 * st + 8 * hl);
 }
-__device__ __forceinline__ void st_image(char* img, const bf16x8 (&f)[2][2], int lane) {
-  const int r = lane & 31, hl = lane >> 5;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-      *reinterpret_cast<bf16x8*>(img + (32 * t + r) * kPitch + (16 * st + 8 * hl) * 2) = f[t][st];
-}
-
 // Lane = query n = 32*qt + r: p[sub][i] = softmax over keys 32*sub + acc_row(i, hl), normalised;
 // mu / inv_l the column's max (0 for a dead query) and 1 / sum (0 for a dead query).
 __device__ __forceinline__ void probs_by_query(const bf16x8 (&kf)[2][2], const bf16x8 (&qf)[2],
@@ -204,15 +159,6 @@ __device__ __forceinline__ void probs_by_query(const bf16x8 (&kf)[2][2], const b
   for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
     for (int i = 0; i < 16; ++i) p[sub][i] *= inv_l;
-}
-
-// accumulator (lane = token column, regs = d rows) -> 8-byte pieces of the token's head slice
-__device__ __forceinline__ void st_cols(__bf16* dst, const f32x16& x, float s, int hl) {
-#pragma unroll
-  for (int ig = 0; ig < 4; ++ig)
-    *reinterpret_cast<uint2*>(dst + 8 * ig + 4 * hl) =
-        make_uint2(pack2(x[4 * ig] * s, x[4 * ig + 1] * s),
-                   pack2(x[4 * ig + 2] * s, x[4 * ig + 3] * s));
 }
 
 __global__ __launch_bounds__(64 * kWinWaves) void winattn_fwd_kernel(Args a) {

@@ -49,12 +49,14 @@ _WIN = 7
 _HEAD_DIM = 32  # the window-attention kernel's head width
 
 
-def _shifts(Hs: int, Ws: int, shift: int):
+def _shifts(Hs: int, Ws: int, shift: int, win: int = _WIN):
     """torchvision's rule: an axis the window covers whole is not shifted."""
-    return (0 if Hs <= _WIN else shift, 0 if Ws <= _WIN else shift)
+    return (0 if Hs <= win else shift, 0 if Ws <= win else shift)
 
 
 class ShiftedWindowAttention(tnn.Module):
+    window = _WIN
+
     def __init__(self, dim: int, heads: int, shift: int):
         super().__init__()
         self.num_heads, self.shift = heads, shift
@@ -70,6 +72,16 @@ class ShiftedWindowAttention(tnn.Module):
                                 self.num_heads, _shifts(Hs, Ws, self.shift))
         return self.proj(a, bias_slot=bias_slot)
 
+    def reference_scores(self, q: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
+        """q, k [B*nW, heads, N, D] -> the scores with the position bias, in plain torch ops."""
+        N = q.shape[-2]
+        a = (q * q.shape[-1] ** -0.5) @ k.transpose(-2, -1)
+        bias = self.relative_position_bias_table[self.relative_position_index]
+        return a + bias.view(N, N, -1).permute(2, 0, 1)
+
+    def reference_qkv_bias(self) -> torch.Tensor:
+        return self.qkv.bias
+
 
 class _MLP(tnn.Sequential):
     """torchvision's ``MLP``: Linear, GELU, Dropout, Linear, Dropout (keys ``0`` and ``3``)."""
@@ -80,10 +92,12 @@ class _MLP(tnn.Sequential):
 
 
 class SwinBlock(tnn.Module):
+    attn_cls = ShiftedWindowAttention
+
     def __init__(self, dim: int, heads: int, shift: int, sd_prob: float):
         super().__init__()
         self.norm1 = mnn.LayerNorm(dim, eps=_EPS)
-        self.attn = ShiftedWindowAttention(dim, heads, shift)
+        self.attn = self.attn_cls(dim, heads, shift)
         self.norm2 = mnn.LayerNorm(dim, eps=_EPS)
         self.mlp = _MLP(dim, 4 * dim)
         self.sd_prob = float(sd_prob)
@@ -118,11 +132,16 @@ class PatchMerging(tnn.Module):
         return self.reduction(self.norm(MF.patch_merge(x, B, Hs, Ws)))
 
 
+def _ln(m, t):
+    return F.layer_norm(t, (t.shape[-1],), m.weight, m.bias, _EPS)
+
+
 class SwinTransformer(tnn.Module):
     """``forward(x)``: x [B, C, H, W] (NCHW, fp32 or bf16) -> logits [B, num_classes] on mipipe's
     kernels; ``reference_forward(x)``: the same parameters (and, in training, the same keep masks)
     through ``torch.roll``, an explicit window partition, ``F.softmax``, ``F.layer_norm`` and
     ``F.linear``."""
+    window, block_cls, merge_cls = _WIN, SwinBlock, PatchMerging
 
     def __init__(self, embed_dim: int, depths: Sequence[int], num_heads: Sequence[int],
                  num_classes: int = 1000, stochastic_depth_prob: float = 0.0, in_chans: int = 3,
@@ -155,11 +174,12 @@ class SwinTransformer(tnn.Module):
             stage = []
             for j in range(n):
                 p = stochastic_depth_prob * done / (total - 1.0) if total > 1 else 0.0
-                stage.append(SwinBlock(dim, heads, 0 if j % 2 == 0 else _WIN // 2, p))
+                shift = 0 if j % 2 == 0 else self.window // 2
+                stage.append(self.block_cls(dim, heads, shift, p))
                 done += 1
             layers.append(tnn.Sequential(*stage))
             if i + 1 < len(depths):
-                layers.append(PatchMerging(dim))
+                layers.append(self.merge_cls(dim))
         self.features = tnn.Sequential(*layers)
         self.norm = mnn.LayerNorm(dims[-1], eps=_EPS)
         self.head = mnn.Linear(dims[-1], num_classes)
@@ -192,12 +212,12 @@ class SwinTransformer(tnn.Module):
             raise ValueError(f"SwinTransformer: expected [B, {self.in_chans}, H, W] input, got "
                              f"{tuple(x.shape)}")
         H, W, n = x.shape[2], x.shape[3], len(self.depths)
-        unit = 4 * _WIN * 2 ** (n - 1)
+        unit = 4 * self.window * 2 ** (n - 1)
         if H % unit or W % unit or H < unit or W < unit:
             raise ValueError(
                 f"SwinTransformer: image {H}x{W}: every stage map must be a whole number of "
-                f"{_WIN}x{_WIN} windows, so H and W must be multiples of {unit} (4-pixel patches, "
-                f"{n - 1} patch mergings); maps are not padded")
+                f"{self.window}x{self.window} windows, so H and W must be multiples of {unit} "
+                f"(4-pixel patches, {n - 1} patch mergings); maps are not padded")
 
     def _path_seeds(self, x: torch.Tensor, advance: bool) -> List:
         """One seed per residual branch (two per block) for this step; see
@@ -259,9 +279,6 @@ class SwinTransformer(tnn.Module):
             seeds = self._last_seeds or self._path_seeds(x, advance=False)
         B = x.shape[0]
 
-        def ln(m, t):
-            return F.layer_norm(t, (t.shape[-1],), m.weight, m.bias, _EPS)
-
         def sd(t, p, seed):
             if not training or p <= 0.0:
                 return t
@@ -269,50 +286,57 @@ class SwinTransformer(tnn.Module):
             inv = torch.tensor(1.0 / (1.0 - p), dtype=torch.float32).to(t.dtype).to(t.device)
             return t * (keep * inv).reshape(-1, 1, 1, 1)
 
-        def attention(at, t):
-            _, H, W, C = t.shape
-            sy, sx = _shifts(H, W, at.shift)
-            if sy or sx:
-                t = torch.roll(t, (-sy, -sx), (1, 2))
-            nW, N, nh = (H // _WIN) * (W // _WIN), _WIN * _WIN, at.num_heads
-            t = t.view(B, H // _WIN, _WIN, W // _WIN, _WIN, C).permute(0, 1, 3, 2, 4, 5)
-            qkv = F.linear(t.reshape(B * nW, N, C), at.qkv.weight, at.qkv.bias)
-            q, k, v = qkv.reshape(B * nW, N, 3, nh, C // nh).permute(2, 0, 3, 1, 4)
-            a = (q * (C // nh) ** -0.5) @ k.transpose(-2, -1)
-            bias = at.relative_position_bias_table[at.relative_position_index]
-            a = a + bias.view(N, N, nh).permute(2, 0, 1)
-            if sy or sx:
-                img = t.new_zeros(H, W)
-                count = 0
-                for hs in ((0, -_WIN), (-_WIN, -sy), (-sy, None)):
-                    for ws in ((0, -_WIN), (-_WIN, -sx), (-sx, None)):
-                        img[hs[0]:hs[1], ws[0]:ws[1]] = count
-                        count += 1
-                img = img.view(H // _WIN, _WIN, W // _WIN, _WIN).permute(0, 2, 1, 3).reshape(nW, N)
-                m = img[:, None, :] - img[:, :, None]
-                m = m.masked_fill(m != 0, -100.0)
-                a = (a.view(B, nW, nh, N, N) + m[None, :, None]).view(B * nW, nh, N, N)
-            o = (F.softmax(a, -1) @ v).transpose(1, 2).reshape(B * nW, N, C)
-            o = F.linear(o, at.proj.weight, at.proj.bias)
-            o = o.view(B, H // _WIN, W // _WIN, _WIN, _WIN, C).permute(0, 1, 3, 2, 4, 5)
-            o = o.reshape(B, H, W, C)
-            return torch.roll(o, (sy, sx), (1, 2)) if sy or sx else o
-
-        h = ln(stem[2], F.conv2d(x, w, stem[0].bias, stride=4).permute(0, 2, 3, 1))
+        h = _ln(stem[2], F.conv2d(x, w, stem[0].bias, stride=4).permute(0, 2, 3, 1))
         site = 0
         for f in list(self.features)[1:]:
             if isinstance(f, PatchMerging):
                 parts = [h[:, 0::2, 0::2], h[:, 1::2, 0::2], h[:, 0::2, 1::2], h[:, 1::2, 1::2]]
-                h = F.linear(ln(f.norm, torch.cat(parts, -1)), f.reduction.weight)
+                h = self._reference_merge(f, torch.cat(parts, -1))
                 continue
             for blk in f:
                 s0, s1 = (seeds[site], seeds[site + 1]) if training else (0, 0)
-                h = h + sd(attention(blk.attn, ln(blk.norm1, h)), blk.sd_prob, s0)
-                y = F.gelu(F.linear(ln(blk.norm2, h), blk.mlp[0].weight, blk.mlp[0].bias))
-                h = h + sd(F.linear(y, blk.mlp[3].weight, blk.mlp[3].bias), blk.sd_prob, s1)
+                h = self._reference_block(blk, h, sd, s0, s1)
                 site += 2
-        y = ln(self.norm, h).mean((1, 2))
+        y = _ln(self.norm, h).mean((1, 2))
         return F.linear(y, self.head.weight, self.head.bias)
+
+    @staticmethod
+    def _reference_merge(f, t):
+        return F.linear(_ln(f.norm, t), f.reduction.weight)
+
+    def _reference_block(self, blk, h, sd, s0, s1):
+        h = h + sd(self._reference_attention(blk.attn, _ln(blk.norm1, h)), blk.sd_prob, s0)
+        y = F.gelu(F.linear(_ln(blk.norm2, h), blk.mlp[0].weight, blk.mlp[0].bias))
+        return h + sd(F.linear(y, blk.mlp[3].weight, blk.mlp[3].bias), blk.sd_prob, s1)
+
+    @staticmethod
+    def _reference_attention(at, t):
+        B, H, W, C = t.shape
+        win = at.window
+        sy, sx = _shifts(H, W, at.shift, win)
+        if sy or sx:
+            t = torch.roll(t, (-sy, -sx), (1, 2))
+        nW, N, nh = (H // win) * (W // win), win * win, at.num_heads
+        t = t.view(B, H // win, win, W // win, win, C).permute(0, 1, 3, 2, 4, 5)
+        qkv = F.linear(t.reshape(B * nW, N, C), at.qkv.weight, at.reference_qkv_bias())
+        q, k, v = qkv.reshape(B * nW, N, 3, nh, C // nh).permute(2, 0, 3, 1, 4)
+        a = at.reference_scores(q, k)
+        if sy or sx:
+            img = t.new_zeros(H, W)
+            count = 0
+            for hs in ((0, -win), (-win, -sy), (-sy, None)):
+                for ws in ((0, -win), (-win, -sx), (-sx, None)):
+                    img[hs[0]:hs[1], ws[0]:ws[1]] = count
+                    count += 1
+            img = img.view(H // win, win, W // win, win).permute(0, 2, 1, 3).reshape(nW, N)
+            m = img[:, None, :] - img[:, :, None]
+            m = m.masked_fill(m != 0, -100.0)
+            a = (a.view(B, nW, nh, N, N) + m[None, :, None]).view(B * nW, nh, N, N)
+        o = (F.softmax(a, -1) @ v).transpose(1, 2).reshape(B * nW, N, C)
+        o = F.linear(o, at.proj.weight, at.proj.bias)
+        o = o.view(B, H // win, W // win, win, win, C).permute(0, 1, 3, 2, 4, 5)
+        o = o.reshape(B, H, W, C)
+        return torch.roll(o, (sy, sx), (1, 2)) if sy or sx else o
 
 
 def _swin(embed_dim, depths, heads, default_sd: float, **kw) -> SwinTransformer:

@@ -530,30 +530,31 @@ def _shift2(shift) -> Tuple[int, int]:
     return (int(shift), int(shift)) if isinstance(shift, int) else (int(shift[0]), int(shift[1]))
 
 
-def window_geometry(Hs: int, Ws: int, shift, device="cpu"):
+def window_geometry(Hs: int, Ws: int, shift, device="cpu", win: int = WIN):
     """(idx [nW, 49], rel [49, 49], mask [nW, 49, 49] bool) of a 7x7 window partition of the map
     rolled by ``-shift``: ``idx[w, n]`` is the row (inside a sample, NHWC order) of token n of
     window w — the token at (wy*7+y, wx*7+x) of the shifted map is ((wy*7+y+sy) % Hs,
     (wx*7+x+sx) % Ws) of the unshifted one; ``rel[i, j] = (yi-yj+6)*13 + (xi-xj+6)`` indexes the
     bias table; ``mask`` is True where the two tokens lie in different ones of the 3x3 shift
-    regions (torchvision's ``shifted_window_attention``; an axis with shift 0 has one region)."""
+    regions (torchvision's ``shifted_window_attention``; an axis with shift 0 has one region).
+    ``win`` = 8 gives Swin V2's 8x8 windows (64 tokens, 225 table rows, shift 0 or 4)."""
     sy, sx = _shift2(shift)
-    if Hs % WIN or Ws % WIN or Hs < WIN or Ws < WIN:
-        raise ValueError(f"the map {Hs}x{Ws} is not a whole number of {WIN}x{WIN} windows")
-    if sy not in (0, 3) or sx not in (0, 3):
-        raise ValueError(f"the shift must be 0 or 3 per axis, got ({sy}, {sx})")
+    if Hs % win or Ws % win or Hs < win or Ws < win:
+        raise ValueError(f"the map {Hs}x{Ws} is not a whole number of {win}x{win} windows")
+    if sy not in (0, win // 2) or sx not in (0, win // 2):
+        raise ValueError(f"the shift must be 0 or {win // 2} per axis, got ({sy}, {sx})")
     Y, X = torch.arange(Hs, device=device), torch.arange(Ws, device=device)
 
-    def part(t):  # [Hs, Ws] of the shifted map -> [nW, 49]
-        return t.reshape(Hs // WIN, WIN, Ws // WIN, WIN).permute(0, 2, 1, 3).reshape(-1, WIN * WIN)
+    def part(t):  # [Hs, Ws] of the shifted map -> [nW, win*win]
+        return t.reshape(Hs // win, win, Ws // win, win).permute(0, 2, 1, 3).reshape(-1, win * win)
 
     idx = part(((Y + sy) % Hs)[:, None] * Ws + ((X + sx) % Ws)[None, :])
-    ry = (Y >= Hs - WIN).long() + (Y >= Hs - sy).long() if sy else torch.zeros_like(Y)
-    rx = (X >= Ws - WIN).long() + (X >= Ws - sx).long() if sx else torch.zeros_like(X)
+    ry = (Y >= Hs - win).long() + (Y >= Hs - sy).long() if sy else torch.zeros_like(Y)
+    rx = (X >= Ws - win).long() + (X >= Ws - sx).long() if sx else torch.zeros_like(X)
     reg = part(ry[:, None] * 3 + rx[None, :])
-    n = torch.arange(WIN * WIN, device=device)
-    y, x = n // WIN, n % WIN
-    rel = (y[:, None] - y[None, :] + WIN - 1) * (2 * WIN - 1) + (x[:, None] - x[None, :] + WIN - 1)
+    n = torch.arange(win * win, device=device)
+    y, x = n // win, n % win
+    rel = (y[:, None] - y[None, :] + win - 1) * (2 * win - 1) + (x[:, None] - x[None, :] + win - 1)
     return idx, rel, reg[:, :, None] != reg[:, None, :]
 
 
@@ -596,6 +597,65 @@ def window_attention(qkv: Tensor, table: Tensor, B: int, Hs: int, Ws: int, heads
     dtable = torch.zeros_like(tab).index_add_(
         0, rel.reshape(-1), ds.sum((0, 1)).permute(1, 2, 0).reshape(N * N, heads))
     return of, dqkv.reshape(B * Hs * Ws, 3 * heads * D).to(qkv.dtype), dtable
+
+
+WIN8 = 8                    # Swin V2's window side
+LOGIT_SCALE_MAX = math.log(100.0)
+NORM_EPS = 1e-12            # F.normalize's
+
+
+def window_attention_v2(qkv: Tensor, bias: Tensor, logit_scale: Tensor, B: int, Hs: int, Ws: int,
+                        heads: int, shift, do: Optional[Tensor] = None):
+    """Swin V2's cosine window attention on the packed projection (csrc/kernels/winattn8.hip):
+    qkv [B*Hs*Ws, 3*heads*32] as :func:`window_attention`, 8x8 windows, bias [225, heads] (the
+    finished continuous-position bias), logit_scale [heads] -> o [B*Hs*Ws, heads*32]; per window
+    and head ``q̂ = q / max(‖q‖, 1e-12)``, k̂ likewise, ``τ = exp(min(logit_scale, ln 100))``,
+    ``P = softmax(τ q̂k̂ᵀ + bias[rel] + (-100 across shift regions))``, ``o = P v``.
+    With ``do`` also the closed-form backward: returns (o, dqkv, dbias, dlogit_scale) with
+    ``dS = P∘(dO Vᵀ - δ)``, ``G = dS∘τ rq rkᵀ``, ``a = rowsum(dS∘τc)``, ``b = colsum(dS∘τc)``,
+    ``dq = G k - q rq² a``, ``dk = Gᵀ q - k rk² b`` (the projection terms vanish where a norm is
+    below eps), ``dbias[rel] = Σ dS``, ``dlogit_scale = Σ a`` (0 where logit_scale > ln 100).
+    fp32 (fp64 for fp64 input)."""
+    idx, rel, msk = window_geometry(Hs, Ws, shift, qkv.device, WIN8)
+    nW, N, D = idx.shape[0], WIN8 * WIN8, WIN_HEAD
+    if qkv.shape != (B * Hs * Ws, 3 * heads * D):
+        raise ValueError(f"qkv must be [{B * Hs * Ws}, {3 * heads * D}], got {tuple(qkv.shape)}")
+    if bias.shape != (rel.max().item() + 1, heads) or logit_scale.numel() != heads:
+        raise ValueError(f"bias must be [225, {heads}] and logit_scale [{heads}], got "
+                         f"{tuple(bias.shape)} and {tuple(logit_scale.shape)}")
+    x = _f(qkv).reshape(B, Hs * Ws, 3, heads, D)[:, idx]  # [B, nW, 64, 3, h, D]
+    tab, ls = bias.to(x.dtype), logit_scale.reshape(heads).to(x.dtype)
+    q, k, v = (x[:, :, :, i].transpose(2, 3) for i in range(3))  # [B, nW, h, 64, D]
+    nq, nk = q.norm(dim=-1, keepdim=True), k.norm(dim=-1, keepdim=True)
+    rq, rk = 1.0 / nq.clamp_min(NORM_EPS), 1.0 / nk.clamp_min(NORM_EPS)
+    tau = torch.exp(ls.clamp(max=LOGIT_SCALE_MAX)).reshape(heads, 1, 1)
+    tc = (q * rq) @ (k * rk).transpose(-1, -2) * tau  # τ·cosines
+    s = tc + tab[rel].permute(2, 0, 1) + (msk.to(tc.dtype) * -100.0)[None, :, None]
+    p = torch.softmax(s, -1)
+    o = p @ v
+
+    def rows(t, out):  # [B, nW, h, 64, D] -> its tokens' rows of out [B, Hs*Ws, h, D]
+        out[:, idx.reshape(-1)] = t.transpose(2, 3).reshape(B, nW * N, heads, D)
+        return out
+
+    of = rows(o, torch.empty(B, Hs * Ws, heads, D, dtype=o.dtype, device=o.device))
+    of = of.reshape(B * Hs * Ws, heads * D).to(qkv.dtype)
+    if do is None:
+        return of
+    dof = _f(do).reshape(B, Hs * Ws, heads, D)[:, idx].transpose(2, 3)
+    dv = p.transpose(-1, -2) @ dof
+    ds = p * (dof @ v.transpose(-1, -2) - (dof * o).sum(-1, keepdim=True))
+    g, w = ds * tau * rq * rk.transpose(-1, -2), ds * tc
+    a, b = w.sum(-1, keepdim=True), w.sum(-2).unsqueeze(-1)
+    dq = g @ k - q * (rq * rq * (nq > NORM_EPS)) * a
+    dk = g.transpose(-1, -2) @ q - k * (rk * rk * (nk > NORM_EPS)) * b
+    dqkv = torch.empty(B, Hs * Ws, 3, heads, D, dtype=o.dtype, device=o.device)
+    for i, t in enumerate((dq, dk, dv)):
+        rows(t, dqkv[:, :, i])
+    dbias = torch.zeros_like(tab).index_add_(
+        0, rel.reshape(-1), ds.sum((0, 1)).permute(1, 2, 0).reshape(N * N, heads))
+    dls = a.sum((0, 1, 3, 4)) * (ls <= LOGIT_SCALE_MAX)
+    return of, dqkv.reshape(B * Hs * Ws, 3 * heads * D).to(qkv.dtype), dbias, dls
 
 
 def patch_merge(x: Tensor, B: int, Hs: int, Ws: int) -> Tensor:

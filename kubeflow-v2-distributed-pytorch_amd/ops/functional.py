@@ -1613,6 +1613,49 @@ def window_attention(qkv: Tensor, table: Tensor, batch: int, hs: int, ws: int, h
                                     int(heads), shift)
 
 
+class _WindowAttentionV2Fn(Function):
+    @staticmethod
+    def forward(ctx, qkv, bias, logit_scale, B, Hs, Ws, heads, shift):
+        ctx.bias_dtype = bias.dtype
+        bias = bias.detach().contiguous()
+        if K.use_native(qkv):
+            bias = bias.float()
+        ctx.save_for_backward(qkv, bias)
+        ctx.logit_scale, ctx.cfg = logit_scale, (B, Hs, Ws, heads, shift)
+        return K.window_attention_v2_fwd(qkv, bias, logit_scale.detach(), B, Hs, Ws, heads, shift)
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, bias = ctx.saved_tensors
+        ls = ctx.logit_scale
+        do = do.contiguous()
+        tt = _direct_grad_target(ls) if K.use_native(do) and ctx.needs_input_grad[2] else None
+        dqkv, db, dl = K.window_attention_v2_bwd(
+            do, qkv, bias, ls.detach(), *ctx.cfg,
+            dlogit_scale=None if tt is None else tt[1].reshape(-1))
+        if tt is not None:
+            tt[0].grad_ready(ls)
+        elif dl is not None:
+            dl = dl.reshape(ls.shape).to(ls.dtype) if ctx.needs_input_grad[2] else None
+        db = db.to(ctx.bias_dtype) if ctx.needs_input_grad[1] else None
+        return dqkv, db, dl, None, None, None, None, None
+
+
+def window_attention_v2(qkv: Tensor, bias: Tensor, logit_scale: Tensor, batch: int, hs: int,
+                        ws: int, heads: int, shift=0) -> Tensor:
+    """Swin V2's (shifted-)window cosine attention over the packed QKV projection output, one
+    kernel each way: qkv [B*Hs*Ws, 3*heads*32] (rows in NHWC token order; q | k | v, head-major),
+    ``bias`` [225, heads] the finished continuous-position bias ``16·sigmoid(cpb_mlp(coords))``
+    (a differentiable tensor: its gradient goes back through the MLP), ``logit_scale`` the fp32
+    parameter ([heads] or [heads, 1, 1]; clamped at ln 100 and exponentiated inside), ``shift`` 0
+    or 4 (or a (y, x) pair) -> o [B*Hs*Ws, heads*32].  8x8 windows; q and k are L2-normalised per
+    token and head in fp32 inside the kernels.  The backward recomputes the probabilities and
+    sums both parameter gradients in a fixed order, ``logit_scale``'s straight into the flat
+    gradient buffer when the parameter lives in one."""
+    return _WindowAttentionV2Fn.apply(qkv.contiguous(), bias, logit_scale, int(batch), int(hs),
+                                      int(ws), int(heads), shift)
+
+
 class _PatchMergeFn(Function):
     @staticmethod
     def forward(ctx, x, B, Hs, Ws):

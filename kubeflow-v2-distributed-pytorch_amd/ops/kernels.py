@@ -30,7 +30,8 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "dwconv7_fwd", "dwconv7_dgrad", "dwconv7_wgrad", "drop_path_keep",
            "scale_residual_fwd", "scale_residual_bwd",
            "bn_act_pool_fwd", "bn_act_pool_bwd_reduce", "bn_act_pool_bwd_apply", "se_scale_fwd",
-           "se_scale_bwd", "window_attention_fwd", "window_attention_bwd", "patch_merge"]
+           "se_scale_bwd", "window_attention_fwd", "window_attention_bwd", "patch_merge",
+           "window_attention_v2_fwd", "window_attention_v2_bwd"]
 
 _ALLOW_REF_ON_GPU = os.environ.get("MIPIPE_ALLOW_REF_ON_GPU", "0") == "1"
 
@@ -602,6 +603,43 @@ def window_attention_bwd(do, qkv, table, B, Hs, Ws, heads, shift, dtable=None):
         dtable.add_(g.reshape(dtable.shape).to(dtable.dtype))
         g = None
     return dqkv, g
+
+
+# ----------------------------------------------------------------------------- winattn8.hip
+def window_attention_v2_fwd(qkv, bias, logit_scale, B, Hs, Ws, heads, shift):
+    """Swin V2's shifted-window cosine attention (8x8 windows, head width 32): qkv as
+    :func:`window_attention_fwd`, ``bias`` fp32 [225, heads] (the finished continuous-position
+    bias), ``logit_scale`` fp32 [heads] (clamped at ln 100 and exponentiated inside), ``shift``
+    0 / 4 or a (y, x) pair -> o [B*Hs*Ws, heads*32] (:func:`_ref.window_attention_v2`).
+    Native: bf16."""
+    sy, sx = _ref._shift2(shift)
+    if use_native(qkv):
+        return native().winattn8_fwd(qkv, bias, logit_scale.reshape(-1), int(B), int(Hs), int(Ws),
+                                     int(heads), sy, sx)
+    return _ref.window_attention_v2(qkv, bias, logit_scale, B, Hs, Ws, heads, (sy, sx))
+
+
+def window_attention_v2_bwd(do, qkv, bias, logit_scale, B, Hs, Ws, heads, shift, dbias=None,
+                            dlogit_scale=None):
+    """-> (dqkv, dbias, dlogit_scale): a parameter gradient (fp32 [225, heads] / [heads]) is
+    ACCUMULATED into its accumulator (returned as None) when one is given.  Native: P is
+    recomputed in the kernel, both parameter gradients are summed in a fixed order — the same
+    bits on every launch, in every mode."""
+    sy, sx = _ref._shift2(shift)
+    if use_native(do):
+        return native().winattn8_bwd(
+            do, qkv, bias, logit_scale.reshape(-1), int(B), int(Hs), int(Ws), int(heads), sy, sx,
+            None if dbias is None else dbias.reshape(-1),
+            None if dlogit_scale is None else dlogit_scale.reshape(-1))
+    _, dqkv, gb, gl = _ref.window_attention_v2(qkv, bias, logit_scale, B, Hs, Ws, heads, (sy, sx),
+                                               do)
+    if dbias is not None:
+        dbias.add_(gb.reshape(dbias.shape).to(dbias.dtype))
+        gb = None
+    if dlogit_scale is not None:
+        dlogit_scale.add_(gl.reshape(dlogit_scale.shape).to(dlogit_scale.dtype))
+        gl = None
+    return dqkv, gb, gl
 
 
 def patch_merge(x, B, Hs, Ws, bwd=False):

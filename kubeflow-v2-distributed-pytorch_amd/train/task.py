@@ -537,10 +537,12 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         kw["stochastic_depth_prob"] = args.stochastic_depth
         kw["seed"] = args.random_seed
     elif args.arch.startswith("swin_"):
-        unit = 112 if args.arch == "swin_nano" else 224
+        win = 8 if args.arch.startswith("swin_v2_") else 7
+        unit = 4 * win * (4 if args.arch.endswith("_nano") else 8)
         if H % unit or W % unit:
             raise SystemExit(f"--arch {args.arch} needs images whose sides are multiples of "
-                             f"{unit} (7x7 windows at every stage; no padding), got {H}x{W}")
+                             f"{unit} ({win}x{win} windows at every stage; no padding), got "
+                             f"{H}x{W}")
         if args.stochastic_depth is not None and not 0.0 <= args.stochastic_depth < 1.0:
             raise SystemExit(f"--stochastic-depth must be in [0, 1), got {args.stochastic_depth}")
         kw["in_chans"] = C

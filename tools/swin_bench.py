@@ -13,13 +13,19 @@ is sampled meanwhile (mipipe/obs/clocks.py).  Per candidate: the µs per call of
 and the median.  ``--resources`` instead compiles winattn.hip for the device and prints the
 compiler's VGPR / LDS / scratch figures per kernel (no GPU needed).
 
-Usage: python tools/swin_bench.py [--batch 64] [--reps 4] [--iters 10]
+``--v2`` measures Swin V2's cosine window attention (winattn8.hip) the same way at swin_v2_t's
+stage shapes, maps 64^2 x 3 heads, 32^2 x 6, 16^2 x 12, 8^2 x 24, shift 0 and 4, against the ATen
+composition of ``SwinTransformerV2.reference_forward`` (F.normalize, the temperature, the gathered
+bias); the output then starts with winattn8.hip's resource figures.
+
+Usage: python tools/swin_bench.py [--v2] [--batch 64] [--reps 4] [--iters 10]
                                   [--out profiles/swin_kernels.txt] | --resources
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import re
 import statistics
@@ -32,16 +38,17 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 STAGES = [(56, 3), (28, 6), (14, 12), (7, 24)]
+STAGES_V2 = [(64, 3), (32, 6), (16, 12), (8, 24)]
 
 
-def resources():
-    """[{kernel, vgprs, agprs, lds_bytes, scratch_bytes, occupancy}] of winattn.hip for gfx950."""
+def resources(src="winattn.hip"):
+    """[{kernel, vgprs, agprs, lds_bytes, scratch_bytes, occupancy}] of a kernel file for gfx950."""
     from tools.build_ext import ARCH, CSRC, HIPCC, _NO_PACKED_FP32
     with tempfile.TemporaryDirectory() as tmp:
         r = subprocess.run(
             [HIPCC, "-O3", "-std=c++17", f"-I{CSRC}", "-DNDEBUG", f"--offload-arch={ARCH}",
              "-munsafe-fp-atomics", *_NO_PACKED_FP32, "-Rpass-analysis=kernel-resource-usage",
-             "-c", os.path.join(CSRC, "kernels", "winattn.hip"), "-o", os.path.join(tmp, "w.o")],
+             "-c", os.path.join(CSRC, "kernels", src), "-o", os.path.join(tmp, "w.o")],
             stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, check=True)
     out, cur = [], None
     for line in r.stdout.splitlines():
@@ -67,11 +74,12 @@ def main(argv=None) -> int:
     ap.add_argument("--iters", type=int, default=10, help="calls per timed loop")
     ap.add_argument("--warmup", type=int, default=2, help="untimed calls per candidate")
     ap.add_argument("--resources", action="store_true")
+    ap.add_argument("--v2", action="store_true", help="Swin V2: winattn8.hip, 8x8 windows")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     a.reps = max(a.reps, 4)
     if a.resources:
-        for rec in resources():
+        for rec in resources("winattn8.hip" if a.v2 else "winattn.hip"):
             print(json.dumps(rec))
         return 0
 
@@ -96,50 +104,89 @@ def main(argv=None) -> int:
         print(s, flush=True)
         lines.append(s)
 
-    def aten_attention(qkv, table, rel, mask, hw, H, shift):
-        """reference_forward's attention on the packed projection, bf16."""
+    W = 8 if a.v2 else 7  # window side
+    N = W * W
+    if a.v2:
+        for rec in resources("winattn8.hip"):
+            emit(rec)
+
+    def aten_attention(qkv, table, rel, mask, hw, H, shift, ls=None):
+        """reference_forward's attention on the packed projection, bf16 (``ls``: V2's logit
+        scales — cosine scores times the clamped temperature instead of the scaled dot product)."""
         x = qkv.view(B, hw, hw, -1)
         if shift:
             x = torch.roll(x, (-shift, -shift), (1, 2))
-        n, nW = hw // 7, (hw // 7) ** 2
-        x = x.view(B, n, 7, n, 7, 3, H, 32).permute(5, 0, 1, 3, 6, 2, 4, 7).reshape(3, B * nW, H, 49, 32)
-        att = (x[0] * 32 ** -0.5) @ x[1].transpose(-2, -1) + table[rel].permute(2, 0, 1).to(bf)
+        n, nW = hw // W, (hw // W) ** 2
+        x = x.view(B, n, W, n, W, 3, H, 32).permute(5, 0, 1, 3, 6, 2, 4, 7).reshape(3, B * nW, H, N, 32)
+        if ls is None:
+            att = (x[0] * 32 ** -0.5) @ x[1].transpose(-2, -1)
+        else:
+            att = F.normalize(x[0], dim=-1) @ F.normalize(x[1], dim=-1).transpose(-2, -1)
+            att = att * torch.clamp(ls, max=math.log(100.0)).exp().to(bf)
+        att = att + table[rel].permute(2, 0, 1).to(bf)
         if shift:
-            att = (att.view(B, nW, H, 49, 49) + mask[None, :, None]).view(B * nW, H, 49, 49)
-        o = (F.softmax(att, -1) @ x[2]).view(B, n, n, H, 7, 7, 32).permute(0, 1, 4, 2, 5, 3, 6)
+            att = (att.view(B, nW, H, N, N) + mask[None, :, None]).view(B * nW, H, N, N)
+        o = (F.softmax(att, -1) @ x[2]).view(B, n, n, H, W, W, 32).permute(0, 1, 4, 2, 5, 3, 6)
         o = o.reshape(B, hw, hw, H * 32)
         return (torch.roll(o, (shift, shift), (1, 2)) if shift else o).reshape(B * hw * hw, -1)
 
     with ClockSampler(0) as cs:
-        for hw, H in STAGES:
-            for shift in (0, 3):
-                if shift and hw == 7:
+        for hw, H in (STAGES_V2 if a.v2 else STAGES):
+            for shift in (0, W // 2):
+                if shift and hw == W:
                     continue  # a single-window map is never shifted
                 torch.manual_seed(0)
                 T, C = B * hw * hw, H * 32
                 qkv = torch.randn(T, 3 * C, device="cuda").to(bf)
                 do = torch.randn(T, C, device="cuda").to(bf)
-                table = torch.randn(169, H, device="cuda") * 0.1
-                dt = torch.zeros(169 * H, device="cuda")
-                _, rel, m = _ref.window_geometry(hw, hw, shift, "cuda")
+                _, rel, m = _ref.window_geometry(hw, hw, shift, "cuda", W)
                 mask = (m * -100.0).to(bf)
-                qa, ta = qkv.clone().requires_grad_(), table.clone().requires_grad_()
+                if a.v2:
+                    table = 16 * torch.sigmoid(torch.randn(225, H, device="cuda"))
+                    ls = torch.full((H, 1, 1), math.log(10.0), device="cuda")
+                    dt, dl = torch.zeros(225, H, device="cuda"), torch.zeros(H, device="cuda")
+                    qa, ta, la = (t.clone().requires_grad_() for t in (qkv, table, ls))
 
-                def aten_fb():
-                    qa.grad = ta.grad = None
-                    aten_attention(qa, ta, rel, mask, hw, H, shift).backward(do)
+                    def aten_fb():
+                        qa.grad = ta.grad = la.grad = None
+                        aten_attention(qa, ta, rel, mask, hw, H, shift, la).backward(do)
 
-                def hip_fb():
-                    K.window_attention_fwd(qkv, table, B, hw, hw, H, shift)
-                    K.window_attention_bwd(do, qkv, table, B, hw, hw, H, shift, dt)
+                    def hip_f():
+                        return K.window_attention_v2_fwd(qkv, table, ls, B, hw, hw, H, shift)
 
+                    def hip_fb():
+                        hip_f()
+                        K.window_attention_v2_bwd(do, qkv, table, ls, B, hw, hw, H, shift, dt, dl)
+
+                    def aten_f():
+                        return aten_attention(qkv, table, rel, mask, hw, H, shift, ls)
+                else:
+                    table = torch.randn(169, H, device="cuda") * 0.1
+                    dt = torch.zeros(169 * H, device="cuda")
+                    qa, ta = qkv.clone().requires_grad_(), table.clone().requires_grad_()
+
+                    def aten_fb():
+                        qa.grad = ta.grad = None
+                        aten_attention(qa, ta, rel, mask, hw, H, shift).backward(do)
+
+                    def hip_f():
+                        return K.window_attention_fwd(qkv, table, B, hw, hw, H, shift)
+
+                    def hip_fb():
+                        hip_f()
+                        K.window_attention_bwd(do, qkv, table, B, hw, hw, H, shift, dt)
+
+                    def aten_f():
+                        return aten_attention(qkv, table, rel, mask, hw, H, shift)
+
+                name = "winattn8" if a.v2 else "winattn"
                 cands = {
-                    "winattn_fwd/hip": lambda: K.window_attention_fwd(qkv, table, B, hw, hw, H, shift),
-                    "winattn_fwd/aten": lambda: aten_attention(qkv, table, rel, mask, hw, H, shift),
-                    "winattn_fwd_bwd/hip": hip_fb,
-                    "winattn_fwd_bwd/aten": aten_fb,
+                    f"{name}_fwd/hip": hip_f,
+                    f"{name}_fwd/aten": aten_f,
+                    f"{name}_fwd_bwd/hip": hip_fb,
+                    f"{name}_fwd_bwd/aten": aten_fb,
                 }
-                if not shift and hw > 7:
+                if not a.v2 and not shift and hw > 7:
                     x = torch.randn(T, C, device="cuda").to(bf)
                     cands["patch_merge_fwd/hip"] = lambda: K.patch_merge(x, B, hw, hw)
                     cands["patch_merge_fwd/aten"] = lambda: _ref.patch_merge(x, B, hw, hw)
