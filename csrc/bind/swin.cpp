@@ -11,22 +11,34 @@ inline void check_aligned16(const Tensor& t, const char* name) {
               " must start on a 16-byte boundary");
 }
 
-// t [B*Hs*Ws, mult*heads*32] bf16 of a window-attention call
-void check_win(const Tensor& t, const char* name, int64_t B, int64_t Hs, int64_t Ws,
-               int64_t heads, int64_t mult, int64_t sy, int64_t sx) {
+// t [B*Hs*Ws, mult*heads*32] bf16 of a window-attention call with win x win windows (op names it)
+void check_win(int64_t win, const char* op, const Tensor& t, const char* name, int64_t B,
+               int64_t Hs, int64_t Ws, int64_t heads, int64_t mult, int64_t sy, int64_t sx) {
+  const int64_t shift = win / 2;
   check_bf16(t, name);
-  TORCH_CHECK(B >= 1 && heads >= 1 && Hs >= 1 && Ws >= 1 && t.numel() > 0,
-              "window_attention: empty input");
-  TORCH_CHECK(Hs % 7 == 0 && Ws % 7 == 0, "window_attention: the map ", Hs, "x", Ws,
-              " is not a whole number of 7x7 windows");
-  TORCH_CHECK((sy == 0 || sy == 3) && (sx == 0 || sx == 3),
-              "window_attention: the shift must be 0 or 3 per axis, got (", sy, ", ", sx, ")");
-  TORCH_CHECK(B * Hs * Ws * 3 * heads * 32 < (1ll << 31),
-              "window_attention: qkv must have fewer than 2^31 elements");
+  TORCH_CHECK(B >= 1 && heads >= 1 && Hs >= 1 && Ws >= 1 && t.numel() > 0, op, ": empty input");
+  TORCH_CHECK(Hs % win == 0 && Ws % win == 0, op, ": the map ", Hs, "x", Ws,
+              " is not a whole number of ", win, "x", win, " windows");
+  TORCH_CHECK((sy == 0 || sy == shift) && (sx == 0 || sx == shift), op,
+              ": the shift must be 0 or ", shift, " per axis, got (", sy, ", ", sx, ")");
+  TORCH_CHECK(B * Hs * Ws * 3 * heads * 32 < (1ll << 31), op,
+              ": qkv must have fewer than 2^31 elements");
   TORCH_CHECK(t.dim() == 2 && t.size(0) == B * Hs * Ws && t.size(1) == mult * heads * 32, name,
               " must be [", B * Hs * Ws, ", ", mult * heads * 32, "] (head width 32), got ",
               t.sizes());
   check_aligned16(t, name);
+}
+
+// where a parameter gradient is accumulated: acc (fp32, n elements, e.g. a flat-gradient view),
+// or a new zeroed buffer of the given shape, left in fresh, when no accumulator is given
+float* grad_target(const optional<Tensor>& acc, optional<Tensor>& fresh, at::IntArrayRef shape,
+                   int64_t n, const Tensor& like) {
+  if (acc.has_value()) {
+    TORCH_CHECK(acc->device() == like.device(), "the accumulator must be on qkv's device");
+    return fptr(acc, n);
+  }
+  fresh = torch::zeros(shape, like.options().dtype(at::kFloat));
+  return fresh->data_ptr<float>();
 }
 
 const float* check_table(const Tensor& table, const Tensor& like, int64_t heads) {
@@ -37,7 +49,7 @@ const float* check_table(const Tensor& table, const Tensor& like, int64_t heads)
 
 Tensor winattn_fwd(Tensor qkv, Tensor table, int64_t B, int64_t Hs, int64_t Ws, int64_t heads,
                    int64_t sy, int64_t sx) {
-  check_win(qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
+  check_win(7, "window_attention", qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
   const float* tp = check_table(table, qkv, heads);
   c10::DeviceGuard g(qkv.device());
   auto o = torch::empty({qkv.size(0), heads * 32}, qkv.options());
@@ -51,24 +63,16 @@ Tensor winattn_fwd(Tensor qkv, Tensor table, int64_t B, int64_t Hs, int64_t Ws, 
 std::tuple<Tensor, optional<Tensor>> winattn_bwd(Tensor dout, Tensor qkv, Tensor table, int64_t B,
                                                  int64_t Hs, int64_t Ws, int64_t heads, int64_t sy,
                                                  int64_t sx, optional<Tensor> dtable_acc) {
-  check_win(qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
-  check_win(dout, "dout", B, Hs, Ws, heads, 1, sy, sx);
+  check_win(7, "window_attention", qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
+  check_win(7, "window_attention", dout, "dout", B, Hs, Ws, heads, 1, sy, sx);
   TORCH_CHECK(dout.device() == qkv.device(), "dout must be on qkv's device");
   const float* tp = check_table(table, qkv, heads);
   c10::DeviceGuard g(qkv.device());
-  auto fo = qkv.options().dtype(at::kFloat);
   optional<Tensor> dtable;
-  float* dt;
-  if (dtable_acc.has_value()) {
-    dt = fptr(dtable_acc, 169 * heads);
-    TORCH_CHECK(dtable_acc->device() == qkv.device(), "the accumulator must be on qkv's device");
-  } else {
-    dtable = torch::zeros({169, heads}, fo);
-    dt = dtable->data_ptr<float>();
-  }
+  float* dt = grad_target(dtable_acc, dtable, {169, heads}, 169 * heads, qkv);
   auto dqkv = torch::empty_like(qkv);
   auto partial = torch::empty({(int64_t)mipipe::winattn_runs(B * (Hs / 7) * (Ws / 7)),
-                               169 * heads}, fo);
+                               169 * heads}, qkv.options().dtype(at::kFloat));
   mipipe::winattn_bwd(dout.data_ptr(), qkv.data_ptr(), tp, dqkv.data_ptr(),
                       partial.data_ptr<float>(), dt, (int)B, (int)Hs, (int)Ws, (int)heads, (int)sy,
                       (int)sx, stream());
@@ -76,23 +80,6 @@ std::tuple<Tensor, optional<Tensor>> winattn_bwd(Tensor dout, Tensor qkv, Tensor
 }
 
 // ---- Swin V2 (winattn8.hip): 8x8 windows, cosine scores
-void check_win8(const Tensor& t, const char* name, int64_t B, int64_t Hs, int64_t Ws,
-                int64_t heads, int64_t mult, int64_t sy, int64_t sx) {
-  check_bf16(t, name);
-  TORCH_CHECK(B >= 1 && heads >= 1 && Hs >= 1 && Ws >= 1 && t.numel() > 0,
-              "window_attention_v2: empty input");
-  TORCH_CHECK(Hs % 8 == 0 && Ws % 8 == 0, "window_attention_v2: the map ", Hs, "x", Ws,
-              " is not a whole number of 8x8 windows");
-  TORCH_CHECK((sy == 0 || sy == 4) && (sx == 0 || sx == 4),
-              "window_attention_v2: the shift must be 0 or 4 per axis, got (", sy, ", ", sx, ")");
-  TORCH_CHECK(B * Hs * Ws * 3 * heads * 32 < (1ll << 31),
-              "window_attention_v2: qkv must have fewer than 2^31 elements");
-  TORCH_CHECK(t.dim() == 2 && t.size(0) == B * Hs * Ws && t.size(1) == mult * heads * 32, name,
-              " must be [", B * Hs * Ws, ", ", mult * heads * 32, "] (head width 32), got ",
-              t.sizes());
-  check_aligned16(t, name);
-}
-
 // bias fp32 [225, heads], logit_scale fp32 [heads] on qkv's device
 void check_win8_params(const Tensor& bias, const Tensor& logit_scale, const Tensor& like,
                        int64_t heads) {
@@ -108,7 +95,7 @@ void check_win8_params(const Tensor& bias, const Tensor& logit_scale, const Tens
 
 Tensor winattn8_fwd(Tensor qkv, Tensor bias, Tensor logit_scale, int64_t B, int64_t Hs,
                     int64_t Ws, int64_t heads, int64_t sy, int64_t sx) {
-  check_win8(qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
+  check_win(8, "window_attention_v2", qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
   check_win8_params(bias, logit_scale, qkv, heads);
   c10::DeviceGuard g(qkv.device());
   auto o = torch::empty({qkv.size(0), heads * 32}, qkv.options());
@@ -125,27 +112,17 @@ std::tuple<Tensor, optional<Tensor>, optional<Tensor>> winattn8_bwd(
     Tensor dout, Tensor qkv, Tensor bias, Tensor logit_scale, int64_t B, int64_t Hs, int64_t Ws,
     int64_t heads, int64_t sy, int64_t sx, optional<Tensor> dbias_acc,
     optional<Tensor> dlogit_acc) {
-  check_win8(qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
-  check_win8(dout, "dout", B, Hs, Ws, heads, 1, sy, sx);
+  check_win(8, "window_attention_v2", qkv, "qkv", B, Hs, Ws, heads, 3, sy, sx);
+  check_win(8, "window_attention_v2", dout, "dout", B, Hs, Ws, heads, 1, sy, sx);
   TORCH_CHECK(dout.device() == qkv.device(), "dout must be on qkv's device");
   check_win8_params(bias, logit_scale, qkv, heads);
   c10::DeviceGuard g(qkv.device());
-  auto fo = qkv.options().dtype(at::kFloat);
   optional<Tensor> dbias, dlogit;
-  auto target = [&](const optional<Tensor>& acc, optional<Tensor>& fresh, at::IntArrayRef shape,
-                    int64_t n) {
-    if (acc.has_value()) {
-      TORCH_CHECK(acc->device() == qkv.device(), "the accumulator must be on qkv's device");
-      return fptr(acc, n);
-    }
-    fresh = torch::zeros(shape, fo);
-    return fresh->data_ptr<float>();
-  };
-  float* db = target(dbias_acc, dbias, {225, heads}, 225 * heads);
-  float* dl = target(dlogit_acc, dlogit, {heads}, heads);
+  float* db = grad_target(dbias_acc, dbias, {225, heads}, 225 * heads, qkv);
+  float* dl = grad_target(dlogit_acc, dlogit, {heads}, heads, qkv);
   auto dqkv = torch::empty_like(qkv);
-  auto partial = torch::empty({(int64_t)mipipe::winattn8_runs(B * (Hs / 8) * (Ws / 8)),
-                               226 * heads}, fo);
+  auto partial = torch::empty({(int64_t)mipipe::winattn_runs(B * (Hs / 8) * (Ws / 8)),
+                               226 * heads}, qkv.options().dtype(at::kFloat));
   mipipe::winattn8_bwd(dout.data_ptr(), qkv.data_ptr(), bias.data_ptr<float>(),
                        logit_scale.data_ptr<float>(), dqkv.data_ptr(), partial.data_ptr<float>(),
                        db, dl, (int)B, (int)Hs, (int)Ws, (int)heads, (int)sy, (int)sx, stream());
@@ -189,13 +166,13 @@ void bind_swin(py::module& m) {
         py::arg("logit_scale"), py::arg("batch"), py::arg("hs"), py::arg("ws"), py::arg("heads"),
         py::arg("shift_y"), py::arg("shift_x"), py::arg("dbias") = py::none(),
         py::arg("dlogit_scale") = py::none());
-  // launch geometry, for the tests' edge shapes
+  // launch geometry, for the tests' edge shapes (one set of constants serves both kernels)
   m.attr("WIN_WAVES") = mipipe::kWinWaves;
   m.attr("WIN_RUN") = mipipe::kWinRun;
   m.attr("WIN_MAX_RUNS") = mipipe::kWinMaxRuns;
-  m.attr("WIN8_WAVES") = mipipe::kWin8Waves;
-  m.attr("WIN8_RUN") = mipipe::kWin8Run;
-  m.attr("WIN8_MAX_RUNS") = mipipe::kWin8MaxRuns;
+  m.attr("WIN8_WAVES") = mipipe::kWinWaves;
+  m.attr("WIN8_RUN") = mipipe::kWinRun;
+  m.attr("WIN8_MAX_RUNS") = mipipe::kWinMaxRuns;
 }
 
 }  // namespace mipipe_bind

@@ -27,12 +27,13 @@
 // (SURVEY.md §2.5 "BASELINE config 4": softmax-attention flash-style fwd/bwd, head_dim 64).
 #include "common.hpp"
 #include "launchers.hpp"
+#include "tile32.hpp"
 
 namespace mipipe {
 namespace attn {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
+using namespace tile32;
+
 constexpr int D = 64;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
@@ -71,24 +72,6 @@ __device__ __forceinline__ bf16x8 ld_tr(const char* img, uint32_t r0, uint32_t c
   return __builtin_bit_cast(bf16x8, v);
 }
 
-__device__ __forceinline__ bf16x8 pack_acc(const f32x16& x, int s) {
-  bf16x8 v;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = (__bf16)x[8 * s + j];
-  return v;
-}
-
-__device__ __forceinline__ f32x16 mfma32(const bf16x8& a, const bf16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
 // counter-based dropout hash (murmur3 finaliser on two mixed words)
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
@@ -97,9 +80,6 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
 __device__ __forceinline__ bool keep_elem(uint32_t seed, uint32_t row_id, uint32_t key, uint32_t thr) {
   return mix32(mix32(seed ^ (row_id * 0x9e3779b1u)) ^ (key * 0x85ebca77u + 0x27d4eb2fu)) >= thr;
 }
-
-// reg i of a 32x32 accumulator <-> row (i&3) + 8(i>>2) + 4h
-__device__ __forceinline__ int acc_row(int i, int hl) { return (i & 3) + 8 * (i >> 2) + 4 * hl; }
 
 struct FwdArgs {
   const __bf16* qkv;

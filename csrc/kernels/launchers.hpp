@@ -488,17 +488,18 @@ void tokens_assemble_fwd(const void* e, const float* cls, const float* pos, void
 // (ascending b, one owner per element: the same bits in every run)
 void tokens_assemble_bwd(const void* dh, void* de, float* dpos, float* dcls, int B, int N, int D,
                          bool f32, hipStream_t st);
-// ---- Swin (winattn.hip) ---------------------------------------------------------------------
-// Shifted-window attention, head width 32, 7x7 windows, bf16: qkv [B*Hs*Ws][3*H*32] (q | k | v,
-// head-major, NHWC token order), o [B*Hs*Ws][H*32], table fp32 [169][H] (the master
-// relative_position_bias_table); sy, sx in {0, 3}: the cyclic shift per axis; Hs % 7 == Ws % 7
-// == 0.  A block = kWinWaves waves of one head, one (window, head) per wave at a time, walking
+// ---- Swin and Swin V2 (winattn.hip, winattn8.hip on wintile.hpp's frame) ---------------------
+// Both: a block = kWinWaves waves of one head, one (window, head) per wave at a time, walking
 // groups of kWinRun windows; at most kWinMaxRuns group slots per head (grid-strided beyond), each
-// with one partial row of the bias-table gradient.
+// with one partial row of the bias gradient.
 constexpr int kWinWaves = 4;
 constexpr int kWinRun = 8;
 constexpr int kWinMaxRuns = 256;
 int winattn_runs(long nwin);  // group slots (= partial rows) of a launch over nwin windows
+// Swin: shifted-window attention, head width 32, 7x7 windows, bf16: qkv [B*Hs*Ws][3*H*32] (q | k
+// | v, head-major, NHWC token order), o [B*Hs*Ws][H*32], table fp32 [169][H] (the master
+// relative_position_bias_table); sy, sx in {0, 3}: the cyclic shift per axis; Hs % 7 == Ws % 7
+// == 0.
 void winattn_fwd(const void* qkv, const float* table, void* o, int B, int Hs, int Ws, int H,
                  int sy, int sx, hipStream_t st);
 // dqkv like qkv (every element written); dtable [169][H] += the bias-table gradient, summed in a
@@ -506,19 +507,14 @@ void winattn_fwd(const void* qkv, const float* table, void* o, int B, int Hs, in
 void winattn_bwd(const void* dout, const void* qkv, const float* table, void* dqkv,
                  float* partial, float* dtable, int B, int Hs, int Ws, int H, int sy, int sx,
                  hipStream_t st);
-// ---- Swin V2 (winattn8.hip) -----------------------------------------------------------------
-// Shifted-window cosine attention, head width 32, 8x8 windows, bf16: qkv / o as above, bias fp32
-// [225][H] (the finished continuous-position bias), logit_scale fp32 [H] (the master parameter:
-// the kernel clamps at ln 100 and exponentiates); sy, sx in {0, 4}; Hs % 8 == Ws % 8 == 0.  The
-// same block / group / slot scheme as above, with constants of its own.
-constexpr int kWin8Waves = 4;
-constexpr int kWin8Run = 8;
-constexpr int kWin8MaxRuns = 256;
-int winattn8_runs(long nwin);  // group slots of a launch over nwin windows
+// Swin V2: shifted-window cosine attention, head width 32, 8x8 windows, bf16: qkv / o as above,
+// bias fp32 [225][H] (the finished continuous-position bias), logit_scale fp32 [H] (the master
+// parameter: the kernel clamps at ln 100 and exponentiates); sy, sx in {0, 4}; Hs % 8 == Ws % 8
+// == 0.
 void winattn8_fwd(const void* qkv, const float* bias, const float* logit_scale, void* o, int B,
                   int Hs, int Ws, int H, int sy, int sx, hipStream_t st);
 // dqkv like qkv (every element written); dbias [225][H] and dlogit_scale [H] += their gradients,
-// summed in a fixed order through partial [winattn8_runs][(225 + 1)*H] (scratch; the 225*H-wide
+// summed in a fixed order through partial [winattn_runs][(225 + 1)*H] (scratch; the 225*H-wide
 // bias rows first, then the H-wide logit_scale rows): no float atomics in any mode
 void winattn8_bwd(const void* dout, const void* qkv, const float* bias, const float* logit_scale,
                   void* dqkv, float* partial, float* dbias, float* dlogit_scale, int B, int Hs,

@@ -1,20 +1,10 @@
 // Swin's shifted-window attention for gfx950: head width 32, 7x7 windows, forward + backward,
 // and the PatchMerging permutation.
 //
-// Layout (the packed-projection convention of attention.hip, rows in NHWC token order):
-//   qkv [B*Hs*Ws][3*H*32] bf16 (q | k | v, head-major), o [B*Hs*Ws][H*32] bf16, dqkv like qkv,
-//   table [169][H] fp32: the master relative_position_bias_table, read as it stands.
-// Per (window, head): P = softmax(q·kᵀ·scale + table[rel(i,j)] + mask(i,j)), o = P·v with
-// rel(i,j) = (yi-yj+6)*13 + (xi-xj+6) and mask = -100 between tokens of different shift regions.
-// The token at (wy*7+y, wx*7+x) of the SHIFTED map is row ((wy*7+y+sy) mod Hs, (wx*7+x+sx) mod Ws)
-// of qkv / o / dqkv: roll, window partition, reverse and un-roll are address arithmetic only.
-//
-// Design: one wave owns one (window, head) at a time; a whole window-head is 49 x 32 (padded to
-// 64 x 32 inside the tile), so scores, softmax, P·V and the full backward live in one wave's
-// registers: no online softmax, no lse, no K/V streaming, no dQ atomics.  A block = kWinWaves
-// waves of ONE head walking groups of kWinRun windows (grid-strided past kWinMaxRuns groups).
-// Per block, once: the head's bias expanded to E[query][key] (log2 domain; dead rows / columns
-// -inf, so padding drops out of every sum as an exact zero) in LDS.
+// Layout, the roll / window / mask addressing, the block's walk over the windows and the
+// bias-table gradient's fixed-order sum are wintile.hpp's frame at WS = 7 (49 live tokens padded
+// to 64 inside the tile); table [169][H] fp32 is the master relative_position_bias_table, read as
+// it stands.  Per (window, head): P = softmax(q·kᵀ·scale + table[rel(i,j)] + mask(i,j)), o = P·v.
 //
 //   forward   Xᵀ = K·Qᵀ on mfma_f32_32x32x16_bf16 (2x2 tiles x 2 k-steps), K / Q fragments loaded
 //             straight from global memory into the operand registers (16-byte loads, no LDS); a
@@ -28,12 +18,7 @@
 //             so no cross-lane reduction), then dVᵀ = dOᵀ·P and dKᵀ = Qᵀ·dS.  Every product uses
 //             "accumulator as the next B operand"; Kᵀ, Qᵀ, dOᵀ come from LDS images by
 //             transposed reads.  dqkv is stored at the same rolled addresses.
-//   dtable    a lane's accumulator registers hold the same (i, j) for every window: the wave
-//             sums dSᵀ over its windows in fp32 registers; at the end the block's waves add their
-//             sums in wave order into one 49 x 49 LDS tile, 169 threads add their diagonal's
-//             entries in index order into the partial row of (group slot, head), and
-//             det_sum_rows adds the partial rows in order into the gradient (+=).  No float
-//             atomics: the same bits on every launch in every mode.
+//   dtable    the wave sums dSᵀ over its windows in fp32 registers (dsum); the frame does the rest.
 #include "common.hpp"
 #include "launchers.hpp"
 #include "wintile.hpp"
@@ -43,89 +28,13 @@ namespace winattn {
 
 using namespace wintile;
 
-constexpr int D = 32;       // head width
-constexpr int WS = 7;       // window side
-constexpr int NT = WS * WS;  // tokens per window (padded to 64 in the tiles)
-constexpr int NREL = (2 * WS - 1) * (2 * WS - 1);
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kMaskLog2 = -100.f * kLog2e;
-constexpr int kEP = 65;               // floats per row of E (conflict-free along both axes)
-constexpr int kERows = NT + 1;        // 49 query rows + one all -inf row for the dead queries
-constexpr int kEBytes = (kERows * kEP * 4 + 15) / 16 * 16;
+constexpr int WS = 7;  // window side
+constexpr int NT = Geo<WS>::NT, NREL = Geo<WS>::NREL, kEBytes = Geo<WS>::kEBytes;
 
-struct Args {
-  const __bf16* qkv;
-  const __bf16* dout;   // backward
-  __bf16* o;            // forward
-  __bf16* dqkv;         // backward
-  const float* table;   // [169][H]
-  float* partial;       // backward: [nruns][169 * H]
-  int Hs, Ws, H, sy, sx, nwy, nwx;
-  int nwin;             // B * nwy * nwx
-  int nruns;            // group slots = gridDim.x / H
+struct Args : WinArgs {
   float scale, scale_log2;
 };
 
-// E[min(q, 49)][k] = table[rel(q, k)][h] * log2e for live (q, k), -inf for dead ones
-__device__ __forceinline__ void fill_bias(float* E, const Args& a, int h, int tid, int nthr) {
-  for (int idx = tid; idx < kERows * 64; idx += nthr) {
-    const int q = idx >> 6, k = idx & 63;
-    float v = -INFINITY;
-    if (q < NT && k < NT) {
-      const int rel = (q / WS - k / WS + WS - 1) * (2 * WS - 1) + (q % WS - k % WS + WS - 1);
-      v = a.table[(long)rel * a.H + h] * kLog2e;
-    }
-    E[q * kEP + k] = v;
-  }
-}
-
-// The lane's part of the region mask, the same bits in both orientations (the relation is
-// symmetric): bit 16*t + i of my / mx <-> tokens n = 32*tile + (lane & 31) and 32*t +
-// acc_row(i, hl) lie on different sides of the axis' shift boundary (7 - shift).
-__device__ __forceinline__ void lane_masks(int tile, int lane, int sy, int sx, uint32_t& my,
-                                           uint32_t& mx) {
-  const int n = min(32 * tile + (lane & 31), NT - 1), hl = lane >> 5;
-  const bool ny = n / WS < WS - sy, nx = n % WS < WS - sx;
-  my = mx = 0;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int m = min(32 * t + acc_row(i, hl), NT - 1);
-      my |= (uint32_t)((m / WS < WS - sy) != ny) << (16 * t + i);
-      mx |= (uint32_t)((m % WS < WS - sx) != nx) << (16 * t + i);
-    }
-}
-
-struct Win {
-  long row[2];      // qkv / o row of token 32*t + (lane & 31) (clamped to the window's last token)
-  bool lasty, lastx;  // the window touches the wrapped border of a shifted axis
-};
-__device__ __forceinline__ Win window(const Args& a, int w, int lane) {
-  const int wx = w % a.nwx, t = w / a.nwx, wy = t % a.nwy, b = t / a.nwy;
-  Win g;
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt) {
-    const int n = min(32 * tt + (lane & 31), NT - 1);
-    int gy = wy * WS + n / WS + a.sy, gx = wx * WS + n % WS + a.sx;
-    gy -= gy >= a.Hs ? a.Hs : 0;
-    gx -= gx >= a.Ws ? a.Ws : 0;
-    g.row[tt] = ((long)b * a.Hs + gy) * a.Ws + gx;
-  }
-  g.lasty = a.sy != 0 && wy == a.nwy - 1;
-  g.lastx = a.sx != 0 && wx == a.nwx - 1;
-  return g;
-}
-
-// the two 16-byte k-steps of token rows' head slice as MFMA operands (row = lane & 31)
-__device__ __forceinline__ void ld_frags(const __bf16* base, const Win& g, long ld, int hl,
-                                         bf16x8 (&f)[2][2]) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-      f[t][st] = *reinterpret_cast<const bf16x8*>(base + g.row[t] * ld + 16 * st + 8 * hl);
-}
 // Lane = query n = 32*qt + r: p[sub][i] = softmax over keys 32*sub + acc_row(i, hl), normalised;
 // mu / inv_l the column's max (0 for a dead query) and 1 / sum (0 for a dead query).
 __device__ __forceinline__ void probs_by_query(const bf16x8 (&kf)[2][2], const bf16x8 (&qf)[2],
@@ -167,17 +76,17 @@ __global__ __launch_bounds__(64 * kWinWaves) void winattn_fwd_kernel(Args a) {
   const int h = blockIdx.x % a.H, run = blockIdx.x / a.H;
   float* E = reinterpret_cast<float*>(smem);
   char* vimg = smem + kEBytes + wave * kImg;
-  fill_bias(E, a, h, tid, 64 * kWinWaves);
+  fill_bias<WS>(E, a, h, tid, 64 * kWinWaves);
   uint32_t my[2], mx[2];
-  lane_masks(0, lane, a.sy, a.sx, my[0], mx[0]);
-  lane_masks(1, lane, a.sy, a.sx, my[1], mx[1]);
+  lane_masks<WS>(0, lane, a.sy, a.sx, my[0], mx[0]);
+  lane_masks<WS>(1, lane, a.sy, a.sx, my[1], mx[1]);
   __syncthreads();
   const long ld = 3l * a.H * D, ldo = (long)a.H * D;
   const __bf16* qb = a.qkv + h * D;
-  const int ngroups = (a.nwin + kWinRun - 1) / kWinRun;
+  const int ngroups = win_groups(a.nwin);
   for (int grp = run; grp < ngroups; grp += a.nruns)
     for (int w = grp * kWinRun + wave; w < min((grp + 1) * kWinRun, a.nwin); w += kWinWaves) {
-      const Win g = window(a, w, lane);
+      const Win g = window<WS>(a, w, lane);
       bf16x8 qf[2][2], kf[2][2], vf[2][2];
       ld_frags(qb, g, ld, hl, qf);
       ld_frags(qb + ldo, g, ld, hl, kf);
@@ -218,20 +127,20 @@ __global__ __launch_bounds__(64 * kWinWaves) void winattn_bwd_kernel(Args a) {
   char* ximg = smem + kEBytes + wave * kBwdWave;
   char* yimg = ximg + kImg;
   float* stat = reinterpret_cast<float*>(yimg + kImg);  // [3][64]
-  fill_bias(E, a, h, tid, 64 * kWinWaves);
+  fill_bias<WS>(E, a, h, tid, 64 * kWinWaves);
   uint32_t my[2], mx[2];
-  lane_masks(0, lane, a.sy, a.sx, my[0], mx[0]);
-  lane_masks(1, lane, a.sy, a.sx, my[1], mx[1]);
+  lane_masks<WS>(0, lane, a.sy, a.sx, my[0], mx[0]);
+  lane_masks<WS>(1, lane, a.sy, a.sx, my[1], mx[1]);
   __syncthreads();
   const long ld = 3l * a.H * D, ldo = (long)a.H * D;
   const __bf16* qb = a.qkv + h * D;
   f32x16 dsum[2][2];  // Σ over this wave's windows of dSᵀ: [query tile][key tile]
 #pragma unroll
   for (int i = 0; i < 4; ++i) dsum[i >> 1][i & 1] = zero16();
-  const int ngroups = (a.nwin + kWinRun - 1) / kWinRun;
+  const int ngroups = win_groups(a.nwin);
   for (int grp = run; grp < ngroups; grp += a.nruns)
     for (int w = grp * kWinRun + wave; w < min((grp + 1) * kWinRun, a.nwin); w += kWinWaves) {
-      const Win g = window(a, w, lane);
+      const Win g = window<WS>(a, w, lane);
       bf16x8 qf[2][2], kf[2][2], vf[2][2], df[2][2];
       ld_frags(qb, g, ld, hl, qf);
       ld_frags(qb + ldo, g, ld, hl, kf);
@@ -314,33 +223,10 @@ __global__ __launch_bounds__(64 * kWinWaves) void winattn_bwd_kernel(Args a) {
         }
       }
     }
-  // ---- bias-table gradient: the waves' sums added in wave order into E (reused), then one
-  // thread per table entry adds its diagonal's (query, key) pairs in index order
-  for (int wv = 0; wv < kWinWaves; ++wv) {
-    __syncthreads();
-    if (wave != wv) continue;
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int qn = 32 * qt + r, kn = 32 * sub + acc_row(i, hl);
-          if (qn < NT) {
-            float* e = E + qn * kEP + kn;
-            *e = wv == 0 ? dsum[qt][sub][i] : *e + dsum[qt][sub][i];
-          }
-        }
-  }
+  // ---- bias-table gradient
+  dsum_to_E<WS>(E, dsum, wave, lane);
   __syncthreads();
-  if (tid < NREL) {
-    const int dy = tid / (2 * WS - 1) - (WS - 1), dx = tid % (2 * WS - 1) - (WS - 1);
-    float acc = 0.f;
-    for (int yq = max(0, dy); yq <= min(WS - 1, WS - 1 + dy); ++yq)
-      for (int xq = max(0, dx); xq <= min(WS - 1, WS - 1 + dx); ++xq)
-        acc += E[(yq * WS + xq) * kEP + (yq - dy) * WS + (xq - dx)];
-    a.partial[(long)run * NREL * a.H + (long)tid * a.H + h] = acc;
-  }
+  if (tid < NREL) st_bias_partial<WS>(E, a, run, h, tid);
 }
 
 // ------------------------------------------------------------------------------ patch_merge
@@ -382,15 +268,9 @@ int winattn_runs(long nwin) {
 static winattn::Args winattn_args(const void* qkv, const float* table, int B, int Hs, int Ws,
                                   int H, int sy, int sx) {
   winattn::Args a{};
-  a.qkv = (const __bf16*)qkv;
-  a.table = table;
-  a.Hs = Hs; a.Ws = Ws; a.H = H; a.sy = sy; a.sx = sx;
-  a.nwy = Hs / winattn::WS;
-  a.nwx = Ws / winattn::WS;
-  a.nwin = B * a.nwy * a.nwx;
-  a.nruns = winattn_runs(a.nwin);
+  wintile::win_geometry<winattn::WS>(a, qkv, table, B, Hs, Ws, H, sy, sx);
   a.scale = 0.17677669529663687f;  // 32^-1/2
-  a.scale_log2 = a.scale * winattn::kLog2e;
+  a.scale_log2 = a.scale * wintile::kLog2e;
   return a;
 }
 

@@ -1,18 +1,15 @@
 // Swin V2's shifted-window cosine attention for gfx950: head width 32, 8x8 windows, forward +
 // backward.
 //
-// Layout as winattn.hip: qkv [B*Hs*Ws][3*H*32] bf16 (q | k | v, head-major, NHWC token rows),
-// o [B*Hs*Ws][H*32] bf16, dqkv like qkv; bias [225][H] fp32, the finished continuous-position
-// bias 16·sigmoid(cpb_mlp(coords)); logit_scale [H] fp32, the master parameter as it stands.
-// Per (window, head): q̂ = q / max(‖q‖, 1e-12), k̂ likewise, τ = exp(min(logit_scale, ln 100)),
-// P = softmax(τ·q̂k̂ᵀ + bias[rel(i,j)] + mask(i,j)), o = P·v with rel(i,j) = (yi-yj+7)*15 +
-// (xi-xj+7) and mask = -100 between tokens of different shift regions (boundary at 8 - shift).
-// The token at (wy*8+y, wx*8+x) of the SHIFTED map is row ((wy*8+y+sy) mod Hs, (wx*8+x+sx) mod Ws).
+// Layout, the roll / window / mask addressing, the block's walk over the windows and the bias
+// gradient's fixed-order sum are wintile.hpp's frame at WS = 8: 64 live tokens fill the tile, so
+// there are no clamped rows and no -inf padding, and E is [64][64] (+1 pitch).  bias [225][H]
+// fp32 is the finished continuous-position bias 16·sigmoid(cpb_mlp(coords)); logit_scale [H] fp32
+// the master parameter as it stands.  Per (window, head): q̂ = q / max(‖q‖, 1e-12), k̂ likewise,
+// τ = exp(min(logit_scale, ln 100)), P = softmax(τ·q̂k̂ᵀ + bias[rel(i,j)] + mask(i,j)), o = P·v.
 //
-// Design: winattn.hip's frame — one wave owns one (window, head), a block = kWin8Waves waves of
-// ONE head walking groups of kWin8Run windows, every product on mfma_f32_32x32x16_bf16 in swapped
-// orientation with the accumulator as the next B operand — with these differences:
-//   * 64 live tokens fill the tile: no clamped rows, no -inf padding, E is [64][64] (+1 pitch).
+// Every product runs on mfma_f32_32x32x16_bf16 in swapped orientation with the accumulator as the
+// next B operand, as in winattn.hip; what the cosine scores change:
 //   * q̂ / k̂ are never formed (no second bf16 rounding): the MFMAs run on the raw q, k and the
 //     fp32 score tile is scaled by rq_i·rk_j·τ.  rq, rk = 1 / max(‖·‖, eps) come from an fp32 sum
 //     of squares of the loaded fragments (16 elements in-lane + one cross-half exchange); the
@@ -28,11 +25,8 @@
 //     the projection terms (in the accumulator's d order) are read from them.
 //   * dlogit_scale[h] = Σ a_i (0 when logit_scale[h] > ln 100: clamp's gradient): a lane sums
 //     its queries' a_i over the wave's windows, then a fixed butterfly over the lanes, the
-//     block's waves in wave order, one entry per (group slot, head).
-//   dbias     as winattn.hip's dtable: fp32 register sums of dSᵀ per wave, the waves added in
-//             wave order into the (reused) E tile, one thread per table entry adds its diagonal
-//             in index order into the partial row of (group slot, head); det_sum_rows adds the
-//             partial rows of both gradients in order (+=).  No float atomics anywhere.
+//     block's waves in wave order, one entry per (group slot, head); det_sum_rows adds the
+//     partial rows of both gradients in order (+=).  No float atomics anywhere.
 #include "common.hpp"
 #include "launchers.hpp"
 #include "wintile.hpp"
@@ -42,88 +36,16 @@ namespace winattn8 {
 
 using namespace wintile;
 
-constexpr int D = 32;       // head width
-constexpr int WS = 8;       // window side
-constexpr int NT = WS * WS;  // tokens per window: the whole 64-row tile
-constexpr int NREL = (2 * WS - 1) * (2 * WS - 1);
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kMaskLog2 = -100.f * kLog2e;
+constexpr int WS = 8;  // window side
+constexpr int NT = Geo<WS>::NT, NREL = Geo<WS>::NREL, kEBytes = Geo<WS>::kEBytes;
 constexpr float kLn100 = 4.605170185988092f;
-constexpr float kEps = 1e-12f;        // F.normalize's
-constexpr int kEP = 65;               // floats per row of E (conflict-free along both axes)
-constexpr int kEBytes = NT * kEP * 4;
-static_assert(NT == 64 && kEBytes % 16 == 0 && NREL < 64 * kWin8Waves, "tile geometry");
+constexpr float kEps = 1e-12f;  // F.normalize's
+static_assert(NT == 64 && NREL < 64 * kWinWaves, "a full tile, and a thread past the table's");
 
-struct Args {
-  const __bf16* qkv;
-  const __bf16* dout;        // backward
-  __bf16* o;                 // forward
-  __bf16* dqkv;              // backward
-  const float* bias;         // [225][H]
+struct Args : WinArgs {
   const float* logit_scale;  // [H]
-  float* partial;            // backward: [nruns][225 * H]
   float* partial_ls;         // backward: [nruns][H]
-  int Hs, Ws, H, sy, sx, nwy, nwx;
-  int nwin;                  // B * nwy * nwx
-  int nruns;                 // group slots = gridDim.x / H
 };
-
-// E[q][k] = bias[rel(q, k)][h] * log2e
-__device__ __forceinline__ void fill_bias(float* E, const Args& a, int h, int tid, int nthr) {
-  for (int idx = tid; idx < NT * NT; idx += nthr) {
-    const int q = idx >> 6, k = idx & 63;
-    const int rel = ((q >> 3) - (k >> 3) + WS - 1) * (2 * WS - 1) + ((q & 7) - (k & 7) + WS - 1);
-    E[q * kEP + k] = a.bias[(long)rel * a.H + h] * kLog2e;
-  }
-}
-
-// The lane's part of the region mask, the same bits in both orientations: bit 16*t + i of my /
-// mx <-> tokens n = 32*tile + (lane & 31) and 32*t + acc_row(i, hl) lie on different sides of
-// the axis' shift boundary (8 - shift).
-__device__ __forceinline__ void lane_masks(int tile, int lane, int sy, int sx, uint32_t& my,
-                                           uint32_t& mx) {
-  const int n = 32 * tile + (lane & 31), hl = lane >> 5;
-  const bool ny = (n >> 3) < WS - sy, nx = (n & 7) < WS - sx;
-  my = mx = 0;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int m = 32 * t + acc_row(i, hl);
-      my |= (uint32_t)(((m >> 3) < WS - sy) != ny) << (16 * t + i);
-      mx |= (uint32_t)(((m & 7) < WS - sx) != nx) << (16 * t + i);
-    }
-}
-
-struct Win {
-  long row[2];        // qkv / o row of token 32*t + (lane & 31)
-  bool lasty, lastx;  // the window touches the wrapped border of a shifted axis
-};
-__device__ __forceinline__ Win window(const Args& a, int w, int lane) {
-  const int wx = w % a.nwx, t = w / a.nwx, wy = t % a.nwy, b = t / a.nwy;
-  Win g;
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt) {
-    const int n = 32 * tt + (lane & 31);
-    int gy = wy * WS + (n >> 3) + a.sy, gx = wx * WS + (n & 7) + a.sx;
-    gy -= gy >= a.Hs ? a.Hs : 0;
-    gx -= gx >= a.Ws ? a.Ws : 0;
-    g.row[tt] = ((long)b * a.Hs + gy) * a.Ws + gx;
-  }
-  g.lasty = a.sy != 0 && wy == a.nwy - 1;
-  g.lastx = a.sx != 0 && wx == a.nwx - 1;
-  return g;
-}
-
-// the two 16-byte k-steps of token rows' head slice as MFMA operands (row = lane & 31)
-__device__ __forceinline__ void ld_frags(const __bf16* base, const Win& g, long ld, int hl,
-                                         bf16x8 (&f)[2][2]) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-      f[t][st] = *reinterpret_cast<const bf16x8*>(base + g.row[t] * ld + 16 * st + 8 * hl);
-}
 
 // rn[t] = 1 / max(‖row 32t + (lane & 31)‖, eps): the lane's 16 elements in fp32, then the other
 // half-wave's 16 (a commutative add: both halves hold the same bits)
@@ -204,25 +126,25 @@ __device__ __forceinline__ float temperature(const Args& a, int h) {
 // LDS per wave, forward: image V | rk[64]
 constexpr int kFwdWave = kImg + 64 * 4;
 
-__global__ __launch_bounds__(64 * kWin8Waves) void winattn8_fwd_kernel(Args a) {
-  __shared__ __attribute__((aligned(16))) char smem[kEBytes + kWin8Waves * kFwdWave];
+__global__ __launch_bounds__(64 * kWinWaves) void winattn8_fwd_kernel(Args a) {
+  __shared__ __attribute__((aligned(16))) char smem[kEBytes + kWinWaves * kFwdWave];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, hl = lane >> 5, r = lane & 31;
   const int h = blockIdx.x % a.H, run = blockIdx.x / a.H;
   float* E = reinterpret_cast<float*>(smem);
   char* vimg = smem + kEBytes + wave * kFwdWave;
   float* rkL = reinterpret_cast<float*>(vimg + kImg);
-  fill_bias(E, a, h, tid, 64 * kWin8Waves);
+  fill_bias<WS>(E, a, h, tid, 64 * kWinWaves);
   const float tau_log2 = temperature(a, h) * kLog2e;
   uint32_t my[2], mx[2];
-  lane_masks(0, lane, a.sy, a.sx, my[0], mx[0]);
-  lane_masks(1, lane, a.sy, a.sx, my[1], mx[1]);
+  lane_masks<WS>(0, lane, a.sy, a.sx, my[0], mx[0]);
+  lane_masks<WS>(1, lane, a.sy, a.sx, my[1], mx[1]);
   __syncthreads();
   const long ld = 3l * a.H * D, ldo = (long)a.H * D;
   const __bf16* qb = a.qkv + h * D;
-  const int ngroups = (a.nwin + kWin8Run - 1) / kWin8Run;
+  const int ngroups = win_groups(a.nwin);
   for (int grp = run; grp < ngroups; grp += a.nruns)
-    for (int w = grp * kWin8Run + wave; w < min((grp + 1) * kWin8Run, a.nwin); w += kWin8Waves) {
-      const Win g = window(a, w, lane);
+    for (int w = grp * kWinRun + wave; w < min((grp + 1) * kWinRun, a.nwin); w += kWinWaves) {
+      const Win g = window<WS>(a, w, lane);
       bf16x8 qf[2][2], kf[2][2], vf[2][2];
       ld_frags(qb, g, ld, hl, qf);
       ld_frags(qb + ldo, g, ld, hl, kf);
@@ -259,9 +181,9 @@ __global__ __launch_bounds__(64 * kWin8Waves) void winattn8_fwd_kernel(Args a) {
 // LDS per wave, backward: images K | Q | dO | per-query max, 1/sum, δ, rq | per-key rk
 constexpr int kBwdWave = 3 * kImg + 5 * 64 * 4;
 
-__global__ __launch_bounds__(64 * kWin8Waves) void winattn8_bwd_kernel(Args a) {
-  __shared__ __attribute__((aligned(16))) char smem[kEBytes + kWin8Waves * kBwdWave];
-  __shared__ float red[kWin8Waves];
+__global__ __launch_bounds__(64 * kWinWaves) void winattn8_bwd_kernel(Args a) {
+  __shared__ __attribute__((aligned(16))) char smem[kEBytes + kWinWaves * kBwdWave];
+  __shared__ float red[kWinWaves];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, hl = lane >> 5, r = lane & 31;
   const int h = blockIdx.x % a.H, run = blockIdx.x / a.H;
   float* E = reinterpret_cast<float*>(smem);
@@ -270,11 +192,11 @@ __global__ __launch_bounds__(64 * kWin8Waves) void winattn8_bwd_kernel(Args a) {
   char* dimg = qimg + kImg;
   float* stat = reinterpret_cast<float*>(dimg + kImg);  // [4][64] by query
   float* rkL = stat + 4 * 64;                           // [64] by key
-  fill_bias(E, a, h, tid, 64 * kWin8Waves);
+  fill_bias<WS>(E, a, h, tid, 64 * kWinWaves);
   const float tau = temperature(a, h);
   uint32_t my[2], mx[2];
-  lane_masks(0, lane, a.sy, a.sx, my[0], mx[0]);
-  lane_masks(1, lane, a.sy, a.sx, my[1], mx[1]);
+  lane_masks<WS>(0, lane, a.sy, a.sx, my[0], mx[0]);
+  lane_masks<WS>(1, lane, a.sy, a.sx, my[1], mx[1]);
   __syncthreads();
   const long ld = 3l * a.H * D, ldo = (long)a.H * D;
   const __bf16* qb = a.qkv + h * D;
@@ -282,10 +204,10 @@ __global__ __launch_bounds__(64 * kWin8Waves) void winattn8_bwd_kernel(Args a) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) dsum[i >> 1][i & 1] = zero16();
   float lsum = 0.f;   // Σ over this wave's windows of a_i of the lane's two queries
-  const int ngroups = (a.nwin + kWin8Run - 1) / kWin8Run;
+  const int ngroups = win_groups(a.nwin);
   for (int grp = run; grp < ngroups; grp += a.nruns)
-    for (int w = grp * kWin8Run + wave; w < min((grp + 1) * kWin8Run, a.nwin); w += kWin8Waves) {
-      const Win g = window(a, w, lane);
+    for (int w = grp * kWinRun + wave; w < min((grp + 1) * kWinRun, a.nwin); w += kWinWaves) {
+      const Win g = window<WS>(a, w, lane);
       bf16x8 qf[2][2], kf[2][2], vf[2][2], df[2][2];
       ld_frags(qb, g, ld, hl, qf);
       ld_frags(qb + ldo, g, ld, hl, kf);
@@ -394,21 +316,8 @@ __global__ __launch_bounds__(64 * kWin8Waves) void winattn8_bwd_kernel(Args a) {
         st_cols(dst + ldo, dv, 1.f, hl);
       }
     }
-  // ---- bias gradient: the waves' sums added in wave order into E (reused), then one thread per
-  // table entry adds its diagonal's (query, key) pairs in index order
-  for (int wv = 0; wv < kWin8Waves; ++wv) {
-    __syncthreads();
-    if (wave != wv) continue;
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          float* e = E + (32 * qt + r) * kEP + 32 * sub + acc_row(i, hl);
-          *e = wv == 0 ? dsum[qt][sub][i] : *e + dsum[qt][sub][i];
-        }
-  }
+  // ---- bias gradient
+  dsum_to_E<WS>(E, dsum, wave, lane);
   // ---- logit_scale gradient: both half-waves hold the same a_i, so one half's 32 lanes in a
   // fixed butterfly, then the waves in wave order
   float ls = hl == 0 ? lsum : 0.f;
@@ -417,38 +326,22 @@ __global__ __launch_bounds__(64 * kWin8Waves) void winattn8_bwd_kernel(Args a) {
   if (lane == 0) red[wave] = ls;
   __syncthreads();
   if (tid < NREL) {
-    const int dy = tid / (2 * WS - 1) - (WS - 1), dx = tid % (2 * WS - 1) - (WS - 1);
-    float acc = 0.f;
-    for (int yq = max(0, dy); yq <= min(WS - 1, WS - 1 + dy); ++yq)
-      for (int xq = max(0, dx); xq <= min(WS - 1, WS - 1 + dx); ++xq)
-        acc += E[(yq * WS + xq) * kEP + (yq - dy) * WS + (xq - dx)];
-    a.partial[(long)run * NREL * a.H + (long)tid * a.H + h] = acc;
+    st_bias_partial<WS>(E, a, run, h, tid);
   } else if (tid == NREL) {
     float acc = red[0];
 #pragma unroll
-    for (int wv = 1; wv < kWin8Waves; ++wv) acc += red[wv];
+    for (int wv = 1; wv < kWinWaves; ++wv) acc += red[wv];
     a.partial_ls[(long)run * a.H + h] = a.logit_scale[h] > kLn100 ? 0.f : acc;
   }
 }
 
 }  // namespace winattn8
 
-int winattn8_runs(long nwin) {
-  const long groups = (nwin + kWin8Run - 1) / kWin8Run;
-  return (int)std::max<long>(1, std::min<long>(groups, kWin8MaxRuns));
-}
-
 static winattn8::Args winattn8_args(const void* qkv, const float* bias, const float* logit_scale,
                                     int B, int Hs, int Ws, int H, int sy, int sx) {
   winattn8::Args a{};
-  a.qkv = (const __bf16*)qkv;
-  a.bias = bias;
+  wintile::win_geometry<winattn8::WS>(a, qkv, bias, B, Hs, Ws, H, sy, sx);
   a.logit_scale = logit_scale;
-  a.Hs = Hs; a.Ws = Ws; a.H = H; a.sy = sy; a.sx = sx;
-  a.nwy = Hs / winattn8::WS;
-  a.nwx = Ws / winattn8::WS;
-  a.nwin = B * a.nwy * a.nwx;
-  a.nruns = winattn8_runs(a.nwin);
   return a;
 }
 
@@ -456,7 +349,7 @@ void winattn8_fwd(const void* qkv, const float* bias, const float* logit_scale, 
                   int Hs, int Ws, int H, int sy, int sx, hipStream_t st) {
   winattn8::Args a = winattn8_args(qkv, bias, logit_scale, B, Hs, Ws, H, sy, sx);
   a.o = (__bf16*)o;
-  hipLaunchKernelGGL(winattn8::winattn8_fwd_kernel, dim3(a.nruns * H), dim3(64 * kWin8Waves), 0,
+  hipLaunchKernelGGL(winattn8::winattn8_fwd_kernel, dim3(a.nruns * H), dim3(64 * kWinWaves), 0,
                      st, a);
 }
 
@@ -468,7 +361,7 @@ void winattn8_bwd(const void* dout, const void* qkv, const float* bias, const fl
   a.dqkv = (__bf16*)dqkv;
   a.partial = partial;
   a.partial_ls = partial + (long)a.nruns * winattn8::NREL * H;
-  hipLaunchKernelGGL(winattn8::winattn8_bwd_kernel, dim3(a.nruns * H), dim3(64 * kWin8Waves), 0,
+  hipLaunchKernelGGL(winattn8::winattn8_bwd_kernel, dim3(a.nruns * H), dim3(64 * kWinWaves), 0,
                      st, a);
   det_sum_rows(a.partial, nullptr, a.nruns, winattn8::NREL * H, dbias, nullptr, true, st);
   det_sum_rows(a.partial_ls, nullptr, a.nruns, H, dlogit_scale, nullptr, true, st);
