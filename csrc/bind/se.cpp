@@ -1,6 +1,6 @@
-// Squeeze-excitation / Hardswish entries of mipipe._C (kernels/se.hip): BatchNorm apply +
-// ReLU / Hardswish with the global average pool in the same pass, its two-pass backward with the
-// pool's gradient as an addend, and the Hardsigmoid gate multiply both ways.
+// Squeeze-excitation entries of mipipe._C (kernels/se.hip): BatchNorm apply + ReLU / Hardswish /
+// SiLU with the global average pool in the same pass, its two-pass backward with the pool's
+// gradient as an addend, and the Hardsigmoid / sigmoid gate multiply both ways.
 #include "bind/common.hpp"
 
 namespace mipipe_bind {
@@ -44,9 +44,15 @@ const float* opt_vec_ptr(const optional<Tensor>& t, int64_t n, const Tensor& ref
   return t.has_value() ? vec_ptr(*t, n, ref, name) : nullptr;
 }
 int check_se_act(int64_t act) {
-  TORCH_CHECK(act == mipipe::kSeActRelu || act == mipipe::kSeActHardswish,
-              "act must be SE_ACT_RELU or SE_ACT_HARDSWISH, got ", act);
+  TORCH_CHECK(act == mipipe::kSeActRelu || act == mipipe::kSeActHardswish ||
+                  act == mipipe::kSeActSilu,
+              "act must be SE_ACT_RELU, SE_ACT_HARDSWISH or SE_ACT_SILU, got ", act);
   return (int)act;
+}
+int check_gate_act(int64_t ga) {
+  TORCH_CHECK(ga == mipipe::kSeGateHardsigmoid || ga == mipipe::kSeGateSigmoid,
+              "gate_act must be SE_GATE_HARDSIGMOID or SE_GATE_SIGMOID, got ", ga);
+  return (int)ga;
 }
 // gate [N, C] (or [N, 1, 1, C]) in x's dtype
 void check_gate(const Tensor& gate, const Tensor& x, const SeArgs& a) {
@@ -135,19 +141,21 @@ Tensor bn_act_pool_bwd_apply(Tensor dz, Tensor y, Tensor scale, Tensor bias, Ten
   return dy;
 }
 
-Tensor se_scale_fwd(Tensor z, Tensor gate) {
+Tensor se_scale_fwd(Tensor z, Tensor gate, int64_t gate_act) {
   const SeArgs a = se_args(z, "z");
+  const int ga = check_gate_act(gate_act);
   check_gate(gate, z, a);
   c10::DeviceGuard g(z.device());
   auto out = torch::empty_like(z);
   mipipe::se_scale_fwd(z.data_ptr(), gate.data_ptr(), out.data_ptr(), a.N, a.HW, a.C, is_f32(z),
-                       stream());
+                       stream(), ga);
   return out;
 }
 
 // -> (dz, dgate); dgate in gate's shape and dtype
-std::tuple<Tensor, Tensor> se_scale_bwd(Tensor dout, Tensor z, Tensor gate) {
+std::tuple<Tensor, Tensor> se_scale_bwd(Tensor dout, Tensor z, Tensor gate, int64_t gate_act) {
   const SeArgs a = se_args(z, "z");
+  const int ga = check_gate_act(gate_act);
   check_like(dout, z, "dout");
   check_gate(gate, z, a);
   c10::DeviceGuard g(z.device());
@@ -155,7 +163,7 @@ std::tuple<Tensor, Tensor> se_scale_bwd(Tensor dout, Tensor z, Tensor gate) {
   auto dgate = torch::empty_like(gate);
   Tensor ws = slice_ws(a, z);
   mipipe::se_scale_bwd(dout.data_ptr(), z.data_ptr(), gate.data_ptr(), dz.data_ptr(),
-                       dgate.data_ptr(), wsp(ws), a.N, a.HW, a.C, is_f32(z), stream());
+                       dgate.data_ptr(), wsp(ws), a.N, a.HW, a.C, is_f32(z), stream(), ga);
   return {dz, dgate};
 }
 
@@ -179,8 +187,10 @@ void bind_se(py::module& m) {
         py::arg("scale"), py::arg("bias"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
         py::arg("act"), py::arg("dpm") = py::none(), py::arg("sum_g") = py::none(),
         py::arg("sum_gx") = py::none());
-  m.def("se_scale_fwd", &se_scale_fwd, py::arg("z"), py::arg("gate"));
-  m.def("se_scale_bwd", &se_scale_bwd, py::arg("dout"), py::arg("z"), py::arg("gate"));
+  m.def("se_scale_fwd", &se_scale_fwd, py::arg("z"), py::arg("gate"),
+        py::arg("gate_act") = (int64_t)mipipe::kSeGateHardsigmoid);
+  m.def("se_scale_bwd", &se_scale_bwd, py::arg("dout"), py::arg("z"), py::arg("gate"),
+        py::arg("gate_act") = (int64_t)mipipe::kSeGateHardsigmoid);
   m.def("se_slices", &se_slices, py::arg("N"), py::arg("HW"), py::arg("C"));
   m.attr("SE_THREADS") = mipipe::kSeThreads;
   m.attr("SE_ROW_U") = mipipe::kSeRowU;
@@ -189,6 +199,9 @@ void bind_se(py::module& m) {
   m.attr("SE_REDUCE_BLOCKS") = mipipe::kSeReduceBlocks;
   m.attr("SE_ACT_RELU") = mipipe::kSeActRelu;
   m.attr("SE_ACT_HARDSWISH") = mipipe::kSeActHardswish;
+  m.attr("SE_ACT_SILU") = mipipe::kSeActSilu;
+  m.attr("SE_GATE_HARDSIGMOID") = mipipe::kSeGateHardsigmoid;
+  m.attr("SE_GATE_SIGMOID") = mipipe::kSeGateSigmoid;
 }
 
 }  // namespace mipipe_bind

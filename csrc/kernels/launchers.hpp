@@ -393,6 +393,9 @@ constexpr int kSeMaxBlocks = 4096;
 constexpr int kSeReduceBlocks = 1024;
 constexpr int kSeActRelu = 1;       // vision.hip's code
 constexpr int kSeActHardswish = 3;
+constexpr int kSeActSilu = 4;       // u * sigmoid(u), sigmoid through expf (not bit-exact to _ref)
+constexpr int kSeGateHardsigmoid = 0;
+constexpr int kSeGateSigmoid = 1;
 struct SeSlices {
   int tpr, rpb, cy;  // threads per row, rows per block pass, grid.y
   int rows, slices;  // rows per slice, slices per sample
@@ -433,13 +436,64 @@ void bn_act_pool_bwd_apply(const void* dz, const void* y, const float* scale, co
                            const float* mean, const float* invstd, const float* gamma,
                            const float* dpm, const float* sum_g, const float* sum_gx, void* dy,
                            int N, int HW, int C, int act, bool f32, hipStream_t st);
-// out = T(z * hardsigmoid(gate[n, c])); gate [N, C] in T
+// out = T(z * s(gate[n, c])); gate [N, C] in T; s = hardsigmoid (kSeGateHardsigmoid) or the
+// logistic sigmoid (kSeGateSigmoid)
 void se_scale_fwd(const void* z, const void* gate, void* out, int N, int HW, int C, bool f32,
-                  hipStream_t st);
-// dz = T(dout * hardsigmoid(gate)), dgate = T((sum_hw dout * z) * hardsigmoid'(gate));
+                  hipStream_t st, int gate_act = kSeGateHardsigmoid);
+// dz = T(dout * s(gate)), dgate = T((sum_hw dout * z) * s'(gate));
 // ws: [N, slices, C] floats when slices > 1
 void se_scale_bwd(const void* dout, const void* z, const void* gate, void* dz, void* dgate,
-                  float* ws, int N, int HW, int C, bool f32, hipStream_t st);
+                  float* ws, int N, int HW, int C, bool f32, hipStream_t st,
+                  int gate_act = kSeGateHardsigmoid);
+
+// ---- depthwise K x K, K in {3, 5}, stride S in {1, 2}, pad (K - 1) / 2, NHWC (dwconvk.hip) ------
+// Forward / weight-grad: a block owns a dwk_tile_h x dwk_tile_w OUTPUT tile of one channel block
+// (kDwkChanBytes of channels: 64 bf16 / 32 fp32) and fills the input halo it needs into LDS once.
+// Stride-2 data-grad: a block owns a kDwkDgradTile^2 tile of dx.  Channel blocks go in grid.y
+// (no channel cap), spatial tiles in grid.x, grid-strided past kDwkMaxBlocks.
+constexpr int kDwkChanBytes = 128;
+constexpr int kDwkMaxBlocks = 2048;
+constexpr int kDwkDgradTile = 16;
+// weight-grad partial rows: kDwkWgradBlocks / channel blocks, in [kDwkWgradMinRows,
+// kDwkWgradMaxRows] and at most the number of tiles
+constexpr int kDwkWgradBlocks = 1024;
+constexpr int kDwkWgradMinRows = 16;
+constexpr int kDwkWgradMaxRows = 512;
+inline bool dwk_supported(int k, int s) { return (k == 3 || k == 5) && (s == 1 || s == 2); }
+inline int dwk_tile_h(int, int) { return 8; }
+inline int dwk_tile_w(int, int s) { return s == 1 ? 16 : 8; }
+inline int dwk_chan_block(bool f32) { return kDwkChanBytes / (f32 ? 4 : 2); }
+inline int dwk_out(int L, int k, int s) { return (L + 2 * ((k - 1) / 2) - k) / s + 1; }
+inline long dwk_tiles(int N, int Ho, int Wo, int k, int s) {
+  const int th = dwk_tile_h(k, s), tw = dwk_tile_w(k, s);
+  return (long)N * ((Ho + th - 1) / th) * ((Wo + tw - 1) / tw);
+}
+// partial rows of the fused BatchNorm statistics: one per forward block of a channel block
+inline int dwk_stat_rows(int N, int Ho, int Wo, int k, int s) {
+  const long t = dwk_tiles(N, Ho, Wo, k, s);
+  return (int)(t < kDwkMaxBlocks ? t : kDwkMaxBlocks);
+}
+inline int dwk_wgrad_rows(int N, int Ho, int Wo, int C, int k, int s, bool f32) {
+  const int cb = dwk_chan_block(f32);
+  long p = kDwkWgradBlocks / ((C + cb - 1) / cb);
+  if (p < kDwkWgradMinRows) p = kDwkWgradMinRows;
+  if (p > kDwkWgradMaxRows) p = kDwkWgradMaxRows;
+  const long t = dwk_tiles(N, Ho, Wo, k, s);
+  return (int)(p < t ? p : t);
+}
+// dynamic LDS bytes of a block: pass 0 forward, 1 data-grad, 2 weight-grad (any dtype)
+int dwk_lds_bytes(int pass, int k, int s);
+// y [N, Ho, Wo, C] = T(sum_taps x * w), w [C, K, K, 1] in T.  shift != null: also the shifted
+// sums of the STORED y, sum (y - shift[c]) -> ps[c] and its square -> pss[c], through ws
+// ([2][dwk_stat_rows][C] partial rows, scratch) summed in a fixed order: no float atomics.
+void dwconvk_fwd(const void* x, const void* w, const float* shift, void* y, float* ws, float* ps,
+                 float* pss, int N, int H, int W, int C, int k, int s, bool f32, hipStream_t st);
+// dx [N, H, W, C] = T(data-grad of dy [N, Ho, Wo, C] (+ addend, fp32, before the rounding))
+void dwconvk_dgrad(const void* dy, const void* w, const void* addend, void* dx, int N, int H,
+                   int W, int C, int k, int s, bool f32, hipStream_t st);
+// dw [C, K*K] += sum dy * x(shifted) through ws ([dwk_wgrad_rows][C*K*K] partial rows, scratch)
+void dwconvk_wgrad(const void* dy, const void* x, float* ws, float* dw, int N, int H, int W, int C,
+                   int k, int s, bool f32, hipStream_t st);
 
 // ---- loss / data ------------------------------------------------------------------------------
 // Launch constants of loss.hip, exported to Python (CE_* / TOP1_*) so that the edge tests derive

@@ -1,11 +1,13 @@
-// Squeeze-excitation and Hardswish kernels (MobileNetV3): BatchNorm apply + ReLU / Hardswish with
-// the SE block's global average pool riding in the same pass, its backward as one reduce + one
-// apply pass that recompute the pre-activation from y (Hardswish's derivative cannot be read
-// from its output) and take the pool's gradient as an addend, and the Hardsigmoid gate multiply
-// both ways.  NHWC, T = bf16 | fp32, C % 8 == 0, 16-byte accesses; geometry: launchers.hpp
-// (se_slices).  Every elementwise result is a fixed sequence of rounded fp32 operations
-// (contraction off: ops/_ref.py reproduces them bit for bit), every sum a fixed-order sum of
-// per-block partial rows: the same bits on every launch, in every mode.
+// Squeeze-excitation kernels (MobileNetV3, EfficientNet): BatchNorm apply + ReLU / Hardswish /
+// SiLU with the SE block's global average pool riding in the same pass, its backward as one
+// reduce + one apply pass that recompute the pre-activation from y (Hardswish's derivative cannot
+// be read from its output, nor can SiLU's) and take the pool's gradient as an addend, and the
+// Hardsigmoid or sigmoid gate multiply both ways.  NHWC, T = bf16 | fp32, C % 8 == 0, 16-byte
+// accesses; geometry: launchers.hpp (se_slices).  Every elementwise result is a fixed sequence of
+// rounded fp32 operations (contraction off: ops/_ref.py reproduces them bit for bit), every sum
+// a fixed-order sum of per-block partial rows: the same bits on every launch, in every mode.
+// The SiLU / sigmoid variants go through expf: a fixed sequence too, but not the bits of
+// ops/_ref.py (tested against float64 within a bound).
 #include "common.hpp"
 #include "launchers.hpp"
 
@@ -14,7 +16,7 @@
 namespace mipipe {
 namespace {
 
-constexpr int kRelu = kSeActRelu, kHswish = kSeActHardswish;
+constexpr int kRelu = kSeActRelu, kHswish = kSeActHardswish, kSilu = kSeActSilu;
 constexpr int U = kSeRowU;
 constexpr int kRedFloats = kSeThreads * 8;  // one [rpb][tpr * 8] array of block partials
 
@@ -104,21 +106,30 @@ __device__ __forceinline__ float se_affine(float y, float sc, float bi) {
   const float t = y * sc;
   return t + bi;
 }
+// the logistic sigmoid through expf: exp(-v) overflowing to inf gives 1 / inf = 0, never a NaN
+__device__ __forceinline__ float se_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 template <int ACT>
 __device__ __forceinline__ float se_act(float u) {
   if constexpr (ACT == kRelu) {
     return fmaxf(u, 0.f);
+  } else if constexpr (ACT == kSilu) {
+    return u * se_sigmoid(u);
   } else {
     const float t = fminf(fmaxf(u + 3.f, 0.f), 6.f);
     return (u * t) / 6.f;
   }
 }
 // e * act'(u) by torch's rules at the knees: ReLU passes u > 0; Hardswish is 0 for u <= -3, the
-// slope (u / 3) + 0.5 inside (-3, 3) and 1 for u >= 3 (what ATen's hardswish_backward returns)
+// slope (u / 3) + 0.5 inside (-3, 3) and 1 for u >= 3 (what ATen's hardswish_backward returns);
+// SiLU is e * (s * (1 + u * (1 - s))), s = sigmoid(u)
 template <int ACT>
 __device__ __forceinline__ float se_act_grad(float u, float e) {
   if constexpr (ACT == kRelu) {
     return u > 0.f ? e : 0.f;
+  } else if constexpr (ACT == kSilu) {
+    const float sg = se_sigmoid(u);
+    const float t = u * (1.f - sg);
+    return e * (sg * (1.f + t));
   } else {
     const float k = (u / 3.f) + 0.5f;
     return u <= -3.f ? 0.f : (u < 3.f ? e * k : e);
@@ -129,6 +140,21 @@ __device__ __forceinline__ float se_hsigmoid(float v) {
 }
 __device__ __forceinline__ float se_hsigmoid_grad(float v) {
   return (v > -3.f && v < 3.f) ? (1.f / 6.f) : 0.f;
+}
+// the gate's activation and its derivative, GATE = kSeGateHardsigmoid | kSeGateSigmoid
+template <int GATE>
+__device__ __forceinline__ float se_gate(float v) {
+  if constexpr (GATE == kSeGateSigmoid) return se_sigmoid(v);
+  else return se_hsigmoid(v);
+}
+template <int GATE>
+__device__ __forceinline__ float se_gate_grad(float v) {
+  if constexpr (GATE == kSeGateSigmoid) {
+    const float sg = se_sigmoid(v);
+    return sg * (1.f - sg);
+  } else {
+    return se_hsigmoid_grad(v);
+  }
 }
 template <class T>
 __device__ __forceinline__ void store1(T* p, float v) { *p = from_f32<T>(v); }
@@ -321,7 +347,7 @@ __global__ __launch_bounds__(kSeThreads) void bn_act_pool_bwd_apply_kernel(
 }
 
 // ---- the gate multiply ------------------------------------------------------------------------
-template <class T>
+template <class T, int GATE>
 __global__ __launch_bounds__(kSeThreads) void se_scale_fwd_kernel(const T* __restrict__ z,
                                                                   const T* __restrict__ gate,
                                                                   T* __restrict__ out, SeGeom g) {
@@ -332,7 +358,7 @@ __global__ __launch_bounds__(kSeThreads) void se_scale_fwd_kernel(const T* __res
     float s[8];
     load8(gate + (long)t.n * g.C + l.c, s);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) s[q] = se_hsigmoid(s[q]);
+    for (int q = 0; q < 8; ++q) s[q] = se_gate<GATE>(s[q]);
     for (int rb = t.r0; rb < t.r1; rb += g.rpb * U) {
       Raw8<T> rz[U];
 #pragma unroll
@@ -353,7 +379,7 @@ __global__ __launch_bounds__(kSeThreads) void se_scale_fwd_kernel(const T* __res
   }
 }
 
-template <class T>
+template <class T, int GATE>
 __global__ __launch_bounds__(kSeThreads) void se_scale_bwd_kernel(
     const T* __restrict__ dout, const T* __restrict__ z, const T* __restrict__ gate,
     T* __restrict__ dz, T* __restrict__ dgate, float* __restrict__ ws, SeGeom g) {
@@ -366,7 +392,7 @@ __global__ __launch_bounds__(kSeThreads) void se_scale_bwd_kernel(
     load8(gate + (long)t.n * g.C + l.c, s);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      s[q] = se_hsigmoid(s[q]);
+      s[q] = se_gate<GATE>(s[q]);
       acc[0][q] = 0.f;
     }
     for (int rb = t.r0; rb < t.r1; rb += g.rpb * U) {
@@ -395,14 +421,14 @@ __global__ __launch_bounds__(kSeThreads) void se_scale_bwd_kernel(
     }
     se_block_sums<1>(acc, red, l, g, [&](int ch, const float* q) {
       const long i = (long)t.n * g.C + ch;
-      if (g.S == 1) store1(dgate + i, q[0] * se_hsigmoid_grad(to_f32(gate[i])));
+      if (g.S == 1) store1(dgate + i, q[0] * se_gate_grad<GATE>(to_f32(gate[i])));
       else ws[(long)u * g.C + ch] = q[0];
     });
   }
 }
 
-// dgate[n, c] = T((sum_s ws[n, s, c]) * hardsigmoid'(gate[n, c])), slices in order
-template <class T>
+// dgate[n, c] = T((sum_s ws[n, s, c]) * gate_act'(gate[n, c])), slices in order
+template <class T, int GATE>
 __global__ __launch_bounds__(256) void se_gate_finish_kernel(const float* __restrict__ ws,
                                                              const T* __restrict__ gate,
                                                              T* __restrict__ dgate, int NC, int C,
@@ -413,7 +439,7 @@ __global__ __launch_bounds__(256) void se_gate_finish_kernel(const float* __rest
     const float* p = ws + (long)n * S * C + c;
     float s = 0.f;
     for (int k = 0; k < S; ++k) s += p[(long)k * C];
-    store1(dgate + i, s * se_hsigmoid_grad(to_f32(gate[i])));
+    store1(dgate + i, s * se_gate_grad<GATE>(to_f32(gate[i])));
   }
 }
 
@@ -421,7 +447,7 @@ inline dim3 se_grid(const SeGeom& g, int cap) {
   return dim3(std::min<uint32_t>(g.units, (uint32_t)cap), (g.C8 + kSeThreads - 1) / kSeThreads);
 }
 inline int finish_grid(long n) { return (int)std::min<long>((n + 255) / 256, kSeMaxBlocks); }
-inline bool se_act_ok(int act) { return act == kRelu || act == kHswish; }
+inline bool se_act_ok(int act) { return act == kRelu || act == kHswish || act == kSilu; }
 
 }  // namespace
 
@@ -431,7 +457,7 @@ void bn_act_pool_fwd(const void* y, const float* scale, const float* bias, void*
   const SeGeom g = se_geom(N, HW, C);
   dispatch_act(f32, [&](auto t) {
     using T = decltype(t);
-    dispatch_int<kRelu, kHswish>(act, [&](auto a) {
+    dispatch_int<kRelu, kHswish, kSilu>(act, [&](auto a) {
       dispatch_bool(pm != nullptr, [&](auto p) {
         hipLaunchKernelGGL((bn_act_pool_fwd_kernel<T, decltype(a)::value, decltype(p)::value>),
                            se_grid(g, kSeMaxBlocks), dim3(kSeThreads), 0, st, (const T*)y, scale,
@@ -454,7 +480,7 @@ void bn_act_pool_bwd_reduce(const void* dz, const void* y, const float* scale, c
   float* ws_gx = ws + (long)P * C;
   dispatch_act(f32, [&](auto t) {
     using T = decltype(t);
-    dispatch_int<kRelu, kHswish>(act, [&](auto a) {
+    dispatch_int<kRelu, kHswish, kSilu>(act, [&](auto a) {
       dispatch_bool(dpm != nullptr, [&](auto d) {
         hipLaunchKernelGGL(
             (bn_act_pool_bwd_reduce_kernel<T, decltype(a)::value, decltype(d)::value>),
@@ -475,7 +501,7 @@ void bn_act_pool_bwd_apply(const void* dz, const void* y, const float* scale, co
   const float inv_cnt = (float)(1.0 / ((double)N * (double)HW));
   dispatch_act(f32, [&](auto t) {
     using T = decltype(t);
-    dispatch_int<kRelu, kHswish>(act, [&](auto a) {
+    dispatch_int<kRelu, kHswish, kSilu>(act, [&](auto a) {
       dispatch_bool(dpm != nullptr, [&](auto d) {
         dispatch_bool(sum_g != nullptr, [&](auto s) {
           hipLaunchKernelGGL((bn_act_pool_bwd_apply_kernel<T, decltype(a)::value,
@@ -490,27 +516,33 @@ void bn_act_pool_bwd_apply(const void* dz, const void* y, const float* scale, co
 }
 
 void se_scale_fwd(const void* z, const void* gate, void* out, int N, int HW, int C, bool f32,
-                  hipStream_t st) {
+                  hipStream_t st, int gate_act) {
   if ((long)N * HW * C <= 0) return;
   const SeGeom g = se_geom(N, HW, C);
   dispatch_act(f32, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(se_scale_fwd_kernel<T>, se_grid(g, kSeMaxBlocks), dim3(kSeThreads), 0, st,
-                       (const T*)z, (const T*)gate, (T*)out, g);
+    dispatch_int<kSeGateHardsigmoid, kSeGateSigmoid>(gate_act, [&](auto ga) {
+      hipLaunchKernelGGL((se_scale_fwd_kernel<T, decltype(ga)::value>), se_grid(g, kSeMaxBlocks),
+                         dim3(kSeThreads), 0, st, (const T*)z, (const T*)gate, (T*)out, g);
+    });
   });
 }
 
 void se_scale_bwd(const void* dout, const void* z, const void* gate, void* dz, void* dgate,
-                  float* ws, int N, int HW, int C, bool f32, hipStream_t st) {
+                  float* ws, int N, int HW, int C, bool f32, hipStream_t st, int gate_act) {
   if ((long)N * HW * C <= 0) return;
   const SeGeom g = se_geom(N, HW, C);
   dispatch_act(f32, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(se_scale_bwd_kernel<T>, se_grid(g, kSeMaxBlocks), dim3(kSeThreads), 0, st,
-                       (const T*)dout, (const T*)z, (const T*)gate, (T*)dz, (T*)dgate, ws, g);
-    if (g.S > 1)
-      hipLaunchKernelGGL(se_gate_finish_kernel<T>, dim3(finish_grid((long)N * C)), dim3(256), 0,
-                         st, ws, (const T*)gate, (T*)dgate, N * C, C, g.S);
+    dispatch_int<kSeGateHardsigmoid, kSeGateSigmoid>(gate_act, [&](auto ga) {
+      constexpr int GA = decltype(ga)::value;
+      hipLaunchKernelGGL((se_scale_bwd_kernel<T, GA>), se_grid(g, kSeMaxBlocks), dim3(kSeThreads),
+                         0, st, (const T*)dout, (const T*)z, (const T*)gate, (T*)dz, (T*)dgate, ws,
+                         g);
+      if (g.S > 1)
+        hipLaunchKernelGGL((se_gate_finish_kernel<T, GA>), dim3(finish_grid((long)N * C)),
+                           dim3(256), 0, st, ws, (const T*)gate, (T*)dgate, N * C, C, g.S);
+    });
   });
 }
 

@@ -21,7 +21,8 @@ from mipipe import nn as mnn
 from mipipe.ops import functional as MF
 from mipipe.ops import kernels as K
 
-__all__ = ["ZooModel", "Exec", "run_seq", "run_module", "conv_bn", "conv_bn_act_pool", "act_of",
+__all__ = ["ZooModel", "Exec", "run_seq", "run_module", "conv_bn", "conv_bn_act_pool",
+           "dwconv_bn_act_pool", "dwconvk_route", "DWCONVK_OLD_ROUTE", "act_of",
            "global_pool",
            "adaptive_avg_pool", "ref_linear"]
 
@@ -46,12 +47,14 @@ def act_of(m) -> str:
         return "relu"
     if isinstance(m, tnn.Hardswish):
         return "hardswish"
+    if isinstance(m, tnn.SiLU):
+        return "silu"
     return "none"
 
 
 def conv_bn_act_pool(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, act: str,
                      pool: bool = False):
-    """(z, pm): z = act(BN(conv(x))), act in {relu, hardswish}, through ``MF.bn_act_pool`` — the
+    """(z, pm): z = act(BN(conv(x))), act in {relu, hardswish, silu}, through ``MF.bn_act_pool`` — the
     activation recomputed from the conv output in the backward, and with ``pool`` the mean of z
     over (h, w) ([N, C] fp32: a squeeze-excitation block's squeeze) from the same pass.  A dense
     conv accumulates the batch statistics in its MFMA epilogue, other convs run the direct
@@ -73,14 +76,47 @@ def conv_bn_act_pool(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, ac
     return MF.bn_act_pool(y, st, bn, act, pool)
 
 
+#: Depthwise shapes (kernel, stride, channels, input rows) at which tools/efficientnet_bench.py
+#: did not see the halo-resident kernel of dwconvk.hip ahead of the generic route (gconv +
+#: chan_stats) in every alternation: :func:`dwconv_bn_act_pool` sends them through the old route.
+DWCONVK_OLD_ROUTE: frozenset = frozenset()
+
+
+def dwconvk_route(x: torch.Tensor, conv: mnn.XConv2d) -> bool:
+    """Whether :func:`dwconv_bn_act_pool` runs ``conv`` on NHWC ``x`` through ``MF.dwconvk``: a
+    bias-free depthwise 3x3 / 5x5 at stride 1 / 2 with "same" padding and C % 8 == 0, at a shape
+    that is not in :data:`DWCONVK_OLD_ROUTE`."""
+    C, k, s = x.shape[-1], conv.kernel_size[0], conv.stride[0]
+    return (conv.groups == C == conv.out_channels and conv.bias is None and k in (3, 5)
+            and conv.kernel_size == (k, k) and conv.stride == (s, s) and s in (1, 2)
+            and conv.padding == ((k - 1) // 2,) * 2 and conv.dilation == (1, 1) and C % 8 == 0
+            and (k, s, C, x.shape[1]) not in DWCONVK_OLD_ROUTE)
+
+
+def dwconv_bn_act_pool(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, act: str,
+                       pool: bool = False, res_give=None):
+    """:func:`conv_bn_act_pool` for a depthwise conv: where :func:`dwconvk_route` holds,
+    ``MF.dwconvk`` (halo-resident kernel, the BatchNorm statistics from the same pass) and then
+    ``MF.bn_act_pool``; elsewhere the generic route.  ``res_give`` (dwconvk route only): x is also
+    the block's residual, whose gradient goes through the slot into this conv's data-grad."""
+    if not dwconvk_route(x, conv):
+        if res_give is not None:
+            raise ValueError("dwconv_bn_act_pool: res_give needs the dwconvk route")
+        return conv_bn_act_pool(x, conv, bn, act, pool)
+    y, ps, pss = MF.dwconvk(x, conv.weight, conv.compute_weight(x.dtype), conv.stride[0],
+                            bn.running_mean if bn.training else None, res_give)
+    st = MF.bn_stats_from_partials(ps, pss, y.numel() // y.shape[-1], bn, bn.training)
+    return MF.bn_act_pool(y, st, bn, act, pool)
+
+
 def conv_bn(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, act: str = "relu",
             residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(BN(conv(x)) [+ residual]).  A dense conv accumulates the BN batch statistics in its
     MFMA epilogue and BN (+residual) (+ReLU) is one elementwise pass; other convs run the
     direct kernel, then the any-C BN pass."""
-    if act == "hardswish":
+    if act in ("hardswish", "silu"):
         if residual is not None:
-            raise NotImplementedError("conv_bn: hardswish with a residual")
+            raise NotImplementedError(f"conv_bn: {act} with a residual")
         return conv_bn_act_pool(x, conv, bn, act)[0]
     cin = x.shape[-1]
     if conv.dense(cin) and act in ("none", "relu") and mnn.fused_eval_applies(bn):
@@ -164,6 +200,8 @@ def run_module(m: tnn.Module, x: torch.Tensor, ex: Exec) -> torch.Tensor:
         return torch.relu(x)
     if isinstance(m, tnn.Hardswish):  # (the [N, 1280] classifier activation of MobileNetV3)
         return F.hardswish(x)
+    if isinstance(m, tnn.SiLU):
+        return F.silu(x)
     if isinstance(m, tnn.Dropout):
         return MF.dropout(x, m.p, ex.seed(), m.training)
     if isinstance(m, tnn.Identity):

@@ -1152,6 +1152,48 @@ def dwconv7_wgrad(dy: Tensor, x: Tensor) -> Tuple[Tensor, Tensor]:
     return dw.reshape(C, 1, 7, 7), g.reshape(-1, C).sum(0)
 
 
+# ---- depthwise K x K, stride 1 / 2 (csrc/kernels/dwconvk.hip)
+def _dwk_args(w: Tensor, stride: int) -> Tuple[int, int]:
+    k = int(w.shape[1])
+    if k not in (3, 5) or w.shape[2] != k or int(stride) not in (1, 2):
+        raise ValueError(f"dwconvk: K must be 3 or 5 and the stride 1 or 2, got K={tuple(w.shape[1:3])}"
+                         f", stride={stride}")
+    return k, (k - 1) // 2
+
+
+def dwconvk_fwd(x: Tensor, w: Tensor, stride: int, shift: Optional[Tensor] = None):
+    """Depthwise K x K (K in {3, 5}), stride 1 / 2, pad (K - 1) / 2, no bias: x [N, H, W, C], w
+    [C, K, K, 1] (``gconv``'s operand layout) -> (y, ps, pss); with ``shift`` [C] ps / pss [1, C]
+    are :func:`chan_stats` of the STORED y (BatchNorm's shifted sums), else None."""
+    k, p = _dwk_args(w, stride)
+    y = F.conv2d(_f(_nchw(x)), _f(_w_oihw(w)), None, stride=int(stride), padding=p,
+                 groups=x.shape[-1])
+    y = _nhwc(y).to(x.dtype)
+    if shift is None:
+        return y, None, None
+    return (y,) + chan_stats(y, shift)
+
+
+def dwconvk_dgrad(dy: Tensor, w: Tensor, x_shape, stride: int,
+                  addend: Optional[Tensor] = None) -> Tensor:
+    """dx [N, H, W, C] of :func:`dwconvk_fwd` (+ ``addend`` in fp32 before the single rounding);
+    input rows / columns no tap reaches get exact zeros."""
+    k, p = _dwk_args(w, stride)
+    N, H, W, C = x_shape
+    dx = _nhwc(torch.nn.grad.conv2d_input((N, C, H, W), _f(_w_oihw(w)), _f(_nchw(dy)),
+                                          stride=int(stride), padding=p, groups=C))
+    if addend is not None:
+        dx = dx + _f(addend)
+    return dx.to(dy.dtype)
+
+
+def dwconvk_wgrad(dy: Tensor, x: Tensor, k: int, stride: int) -> Tensor:
+    """dw [C, 1, K, K] in fp32 (fp64 inputs stay fp64)."""
+    C = x.shape[-1]
+    return torch.nn.grad.conv2d_weight(_f(_nchw(x)), (C, 1, k, k), _f(_nchw(dy)),
+                                       stride=int(stride), padding=(k - 1) // 2, groups=C)
+
+
 def drop_path_keep(n: int, p: float, seed: int, device="cpu") -> Tensor:
     """[n] keep mask of stochastic depth in "row" mode: the dropout hash (:func:`dropout_keep`)
     applied to the sample index, so it depends only on (seed, sample)."""
@@ -1218,25 +1260,38 @@ def _se_pre(y: Tensor, scale: Tensor, bias: Tensor) -> Tensor:
     return (_f(y) * scale.to(dt)) + bias.to(dt)
 
 
+def sigmoid(v: Tensor) -> Tensor:
+    """1 / (1 + exp(-v)) as the kernels form it: exp(-v) = inf gives 0, never a NaN.  (The
+    kernels' expf is not torch's exp: these variants agree to a bound, not bit for bit.)"""
+    return 1.0 / (1.0 + torch.exp(-v))
+
+
 def se_act(u: Tensor, act: str) -> Tensor:
-    """relu: max(u, 0); hardswish: (u * clamp(u + 3, 0, 6)) / 6 with a true division."""
+    """relu: max(u, 0); hardswish: (u * clamp(u + 3, 0, 6)) / 6 with a true division; silu:
+    u * sigmoid(u)."""
     if act == "relu":
         return torch.relu(u)
     if act == "hardswish":
         return (u * (u + 3.0).clamp(0.0, 6.0)) / _const(6.0, u)
-    raise ValueError(f"bn_act_pool: act must be relu or hardswish, got {act!r}")
+    if act == "silu":
+        return u * sigmoid(u)
+    raise ValueError(f"bn_act_pool: act must be relu, hardswish or silu, got {act!r}")
 
 
 def se_act_grad(u: Tensor, e: Tensor, act: str) -> Tensor:
     """e * act'(u) by torch's rules at the knees (what ATen's backward kernels return).  relu:
-    u > 0.  hardswish: 0 for u <= -3, e * ((u / 3) + 0.5) for -3 < u < 3, e for u >= 3."""
+    u > 0.  hardswish: 0 for u <= -3, e * ((u / 3) + 0.5) for -3 < u < 3, e for u >= 3.  silu:
+    e * (s * (1 + u * (1 - s))), s = sigmoid(u)."""
     zero = torch.zeros_like(e)
     if act == "relu":
         return torch.where(u > 0, e, zero)
+    if act == "silu":
+        sg = sigmoid(u)
+        return e * (sg * (1.0 + u * (1.0 - sg)))
     if act == "hardswish":
         mid = e * ((u / _const(3.0, u)) + 0.5)
         return torch.where(u <= -3.0, zero, torch.where(u < 3.0, mid, e))
-    raise ValueError(f"bn_act_pool: act must be relu or hardswish, got {act!r}")
+    raise ValueError(f"bn_act_pool: act must be relu, hardswish or silu, got {act!r}")
 
 
 def hardsigmoid(gate: Tensor) -> Tensor:
@@ -1293,20 +1348,32 @@ def bn_act_pool_bwd_apply(dz: Tensor, y: Tensor, scale: Tensor, bias: Tensor, me
     return (k * ((g - sum_g.to(g.dtype) * inv) - xhat * (sum_gx.to(g.dtype) * inv))).to(dz.dtype)
 
 
-def se_scale_fwd(z: Tensor, gate: Tensor) -> Tensor:
-    """out = T(fp32(z) * s), s = hardsigmoid(gate[n, c]); gate [N, C] or [N, 1, 1, C]."""
+def _gate(gate: Tensor, gate_act: str) -> Tensor:
+    if gate_act == "hardsigmoid":
+        return hardsigmoid(gate)
+    if gate_act == "sigmoid":
+        return sigmoid(_f(gate))
+    raise ValueError(f"se_scale: gate_act must be hardsigmoid or sigmoid, got {gate_act!r}")
+
+
+def se_scale_fwd(z: Tensor, gate: Tensor, gate_act: str = "hardsigmoid") -> Tensor:
+    """out = T(fp32(z) * s), s = hardsigmoid | sigmoid (gate[n, c]); gate [N, C] or [N, 1, 1, C]."""
     N, H, W, C = z.shape
-    return (_f(z) * hardsigmoid(gate).reshape(N, 1, 1, C)).to(z.dtype)
+    return (_f(z) * _gate(gate, gate_act).reshape(N, 1, 1, C)).to(z.dtype)
 
 
-def se_scale_bwd(dout: Tensor, z: Tensor, gate: Tensor) -> Tuple[Tensor, Tensor]:
+def se_scale_bwd(dout: Tensor, z: Tensor, gate: Tensor,
+                 gate_act: str = "hardsigmoid") -> Tuple[Tensor, Tensor]:
     """(dz, dgate): dz = T(fp32(dout) * s); dgate = T(q * s'), q[n, c] = sum_hw fp32(dout) *
-    fp32(z), s' = fp32(1 / 6) for -3 < gate < 3, else 0."""
+    fp32(z); hardsigmoid: s' = fp32(1 / 6) for -3 < gate < 3, else 0; sigmoid: s' = s * (1 - s)."""
     N, H, W, C = z.shape
     d = _f(dout)
-    dz = (d * hardsigmoid(gate).reshape(N, 1, 1, C)).to(z.dtype)
+    dz = (d * _gate(gate, gate_act).reshape(N, 1, 1, C)).to(z.dtype)
     q = (d * _f(z)).reshape(N, H * W, C).sum(1)
     gf = _f(gate).reshape(N, C)
+    if gate_act == "sigmoid":
+        sg = sigmoid(gf)
+        return dz, (q * (sg * (1.0 - sg))).reshape(gate.shape).to(gate.dtype)
     # fp32(1 / 6) in every precision, as the kernel's constant and ATen's hardsigmoid backward
     sixth = torch.tensor(1.0 / 6.0, dtype=torch.float32).to(device=gf.device, dtype=gf.dtype)
     sp = torch.where((gf > -3.0) & (gf < 3.0), sixth, torch.zeros_like(sixth))

@@ -1373,6 +1373,53 @@ class _DwConv7Fn(Function):
         return dx, dw, None, db, None
 
 
+class _DwConvKFn(Function):
+    """Depthwise 3x3 / 5x5 at stride 1 / 2 on the halo-resident kernels of dwconvk.hip, with
+    BatchNorm's shifted statistics from the forward pass.  The data-grad adds a gradient handed
+    over through ``res_give``; the weight gradient accumulates straight into the flat DDP gradient
+    buffer when the parameter lives there (fixed-order sums: no float atomics in any mode)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, w_c, stride, shift, res_give):
+        y, ps, pss = K.dwconvk_fwd(x, w_c, stride, shift)
+        ctx.save_for_backward(x, w_c)
+        ctx.weight, ctx.stride, ctx.res_give = weight, stride, res_give
+        ctx.mark_non_differentiable(*[t for t in (ps, pss) if t is not None])
+        return y, ps, pss
+
+    @staticmethod
+    def backward(ctx, dy, _g1, _g2):
+        x, w_c = ctx.saved_tensors
+        weight, stride = ctx.weight, ctx.stride
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            add = ctx.res_give.take() if ctx.res_give is not None else None
+            if add is not None:
+                add = add.reshape(x.shape).to(dy.dtype)
+            dx = K.dwconvk_dgrad(dy, w_c, x.shape, stride, add)
+        if ctx.needs_input_grad[1]:
+            tw = _direct_grad_target(weight) if K.use_native(dy) else None
+            g_w = K.dwconvk_wgrad(dy, x, w_c.shape[1], stride,
+                                  None if tw is None else tw[1].reshape(-1))
+            if tw is not None:
+                tw[0].grad_ready(weight)
+            else:
+                dw = g_w.reshape(weight.shape).to(weight.dtype)
+        return dx, dw, None, None, None, None
+
+
+def dwconvk(x: Tensor, weight: Tensor, w_c: Tensor, stride: int,
+            stats_shift: Optional[Tensor] = None, res_give: Optional["ResidualSlot"] = None):
+    """``(y, ps, pss)``: depthwise K x K (K in {3, 5}), stride 1 / 2, pad (K - 1) / 2, no bias, on
+    NHWC ``x``; ``weight`` [C, 1, K, K]: the parameter (gradient target), ``w_c`` [C, K, K, 1]: the
+    compute-dtype operand.  With ``stats_shift`` (fp32 [C], BatchNorm's running mean) ps / pss are
+    the shifted sums :func:`bn_stats_from_partials` consumes, from the same pass.  ``res_give``: x
+    is also a residual whose gradient was given to the slot; this layer's data-grad adds it."""
+    return _DwConvKFn.apply(x.contiguous(), weight, w_c, int(stride),
+                            None if stats_shift is None else stats_shift.detach(), res_give)
+
+
 def dwconv7(x: Tensor, weight: Tensor, w_c: Tensor, bias: Optional[Tensor],
             res_give: Optional["ResidualSlot"] = None) -> Tensor:
     """Depthwise 7x7, stride 1, pad 3 on NHWC ``x``; ``weight`` [C, 1, 7, 7] / ``bias``: the
@@ -1472,7 +1519,7 @@ class _BNActPoolFn(Function):
 def bn_act_pool(y: Tensor, st: BNStats, bn, act: str, pool: bool = False):
     """``(z, pm)``: z = act(BatchNorm(y)) for NHWC ``y`` with the statistics ``st`` (of the MFMA
     conv epilogue, or :func:`K.chan_stats` + :func:`bn_stats_from_partials`), act in {relu,
-    hardswish}; with ``pool`` also pm [N, C] fp32, the mean of z over (h, w) — the
+    hardswish, silu}; with ``pool`` also pm [N, C] fp32, the mean of z over (h, w) — the
     squeeze-excitation block's squeeze — else None.  The backward takes both gradients and makes
     a single reduce + apply pair: the pool's backward is an addend inside them."""
     return _BNActPoolFn.apply(y.contiguous(), bn.weight, bn.bias, st, act, bool(pool))
@@ -1480,20 +1527,21 @@ def bn_act_pool(y: Tensor, st: BNStats, bn, act: str, pool: bool = False):
 
 class _SeScaleFn(Function):
     @staticmethod
-    def forward(ctx, z, gate):
+    def forward(ctx, z, gate, gate_act):
         ctx.save_for_backward(z, gate)
-        return K.se_scale_fwd(z, gate)
+        ctx.gate_act = gate_act
+        return K.se_scale_fwd(z, gate, gate_act)
 
     @staticmethod
     def backward(ctx, dout):
         z, gate = ctx.saved_tensors
-        return K.se_scale_bwd(dout.contiguous(), z, gate)
+        return K.se_scale_bwd(dout.contiguous(), z, gate, ctx.gate_act) + (None,)
 
 
-def se_scale(z: Tensor, gate: Tensor) -> Tensor:
-    """``z * hardsigmoid(gate)``: NHWC ``z``, ``gate`` [N, C] or [N, 1, 1, C] in z's dtype (the
-    squeeze-excitation block's excite); one kernel each way."""
-    return _SeScaleFn.apply(z.contiguous(), gate.contiguous())
+def se_scale(z: Tensor, gate: Tensor, gate_act: str = "hardsigmoid") -> Tensor:
+    """``z * gate_act(gate)``, gate_act in {hardsigmoid, sigmoid}: NHWC ``z``, ``gate`` [N, C] or
+    [N, 1, 1, C] in z's dtype (the squeeze-excitation block's excite); one kernel each way."""
+    return _SeScaleFn.apply(z.contiguous(), gate.contiguous(), gate_act)
 
 
 class _TokensAssembleFn(Function):

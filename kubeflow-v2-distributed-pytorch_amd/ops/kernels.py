@@ -28,6 +28,7 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "gconv_fwd", "gconv_dgrad", "gconv_wgrad", "chan_stats", "affine_act",
            "bn_generic_bwd_reduce", "bn_generic_bwd_apply", "avgpool2d_fwd", "avgpool2d_bwd",
            "dwconv7_fwd", "dwconv7_dgrad", "dwconv7_wgrad", "drop_path_keep",
+           "dwconvk_fwd", "dwconvk_dgrad", "dwconvk_wgrad",
            "scale_residual_fwd", "scale_residual_bwd",
            "bn_act_pool_fwd", "bn_act_pool_bwd_reduce", "bn_act_pool_bwd_apply", "se_scale_fwd",
            "se_scale_bwd", "window_attention_fwd", "window_attention_bwd", "patch_merge",
@@ -952,6 +953,39 @@ def dwconv7_wgrad(dy, x, dw=None, dbias=None):
     return g_w, g_b
 
 
+# ----------------------------------------------------------------------------- dwconvk.hip
+def dwconvk_fwd(x, w, stride, shift=None):
+    """Depthwise K x K (K in {3, 5}), stride 1 / 2, pad (K - 1) / 2, no bias, on NHWC ``x``: ``w``
+    [C, K, K, 1] in x's dtype (:func:`gconv_fwd`'s operand, read as it stands) -> (y, ps, pss).
+    With ``shift`` (fp32 [C]) ps / pss [1, C] are :func:`chan_stats` of the stored y, summed in the
+    same pass in a fixed order (the same bits on every launch), else None.  Native: C % 8 == 0."""
+    if use_native(x):
+        return native().dwconvk_fwd(x, w, int(stride), shift)
+    return _ref.dwconvk_fwd(x, w, stride, shift)
+
+
+def dwconvk_dgrad(dy, w, x_shape, stride, addend=None):
+    """dx [N, H, W, C] of :func:`dwconvk_fwd`; ``addend`` (dx's shape and dtype) is added in fp32
+    before the single rounding."""
+    if use_native(dy):
+        return native().dwconvk_dgrad(dy, w, list(x_shape), int(stride),
+                                      None if addend is None else addend.contiguous())
+    return _ref.dwconvk_dgrad(dy, w, x_shape, stride, addend)
+
+
+def dwconvk_wgrad(dy, x, k, stride, dw=None):
+    """-> dw [C, 1, K, K] fp32, ACCUMULATED into ``dw`` (C*K*K floats: a flat-gradient view;
+    returned as None) when given.  Native: one launch, per-block partial rows summed in a fixed
+    order — no float atomics, the same bits on every launch, in every mode."""
+    if use_native(dy):
+        return native().dwconvk_wgrad(dy, x, int(k), int(stride), dw)
+    g_w = _ref.dwconvk_wgrad(dy, x, k, stride)
+    if dw is not None:
+        dw.add_(g_w.reshape(dw.shape).to(dw.dtype))
+        return None
+    return g_w
+
+
 def _path_seed(seed) -> int:
     """The host seed of a stochastic-depth site (a :class:`DevSeed`'s counter folded in as the
     kernels fold it)."""
@@ -997,17 +1031,24 @@ def scale_residual_bwd(dout, f, gamma, hw, p=0.0, seed=0, dgamma=None, dbias=Non
 
 
 # ----------------------------------------------------------------------------- se.hip
-_SE_ACT = {"relu": 1, "hardswish": 3}  # SE_ACT_RELU, SE_ACT_HARDSWISH
+_SE_ACT = {"relu": 1, "hardswish": 3, "silu": 4}  # SE_ACT_RELU, SE_ACT_HARDSWISH, SE_ACT_SILU
+_SE_GATE = {"hardsigmoid": 0, "sigmoid": 1}  # SE_GATE_HARDSIGMOID, SE_GATE_SIGMOID
 
 
 def _se_act(act: str) -> int:
     if act not in _SE_ACT:
-        raise ValueError(f"bn_act_pool: act must be relu or hardswish, got {act!r}")
+        raise ValueError(f"bn_act_pool: act must be relu, hardswish or silu, got {act!r}")
     return _SE_ACT[act]
 
 
+def _se_gate(gate_act: str) -> int:
+    if gate_act not in _SE_GATE:
+        raise ValueError(f"se_scale: gate_act must be hardsigmoid or sigmoid, got {gate_act!r}")
+    return _SE_GATE[gate_act]
+
+
 def bn_act_pool_fwd(y, scale, bias, act, want_pool=False):
-    """-> (z, pm): z = T(act(y * scale[c] + bias[c])) for NHWC ``y``, act in {relu, hardswish};
+    """-> (z, pm): z = T(act(y * scale[c] + bias[c])) for NHWC ``y``, act in {relu, hardswish, silu};
     with ``want_pool`` also pm [N, C] fp32, the mean over (h, w) of the stored z — the SE block's
     global average pool in the BatchNorm apply pass (:func:`_ref.bn_act_pool_fwd`, z bit for
     bit).  Native: C % 8 == 0."""
@@ -1037,17 +1078,18 @@ def bn_act_pool_bwd_apply(dz, y, scale, bias, mean, invstd, gamma, act, dpm=None
                                       sum_gx)
 
 
-def se_scale_fwd(z, gate):
-    """out = T(z * hardsigmoid(gate[n, c])): NHWC ``z``, ``gate`` [N, C] or [N, 1, 1, C] in z's
-    dtype (:func:`_ref.se_scale_fwd`, bit for bit)."""
+def se_scale_fwd(z, gate, gate_act="hardsigmoid"):
+    """out = T(z * s(gate[n, c])), s = ``gate_act`` in {hardsigmoid, sigmoid}: NHWC ``z``, ``gate``
+    [N, C] or [N, 1, 1, C] in z's dtype (:func:`_ref.se_scale_fwd`; hardsigmoid bit for bit,
+    sigmoid to the rounding of expf)."""
     if use_native(z):
-        return native().se_scale_fwd(z, gate)
-    return _ref.se_scale_fwd(z, gate)
+        return native().se_scale_fwd(z, gate, _se_gate(gate_act))
+    return _ref.se_scale_fwd(z, gate, gate_act)
 
 
-def se_scale_bwd(dout, z, gate):
+def se_scale_bwd(dout, z, gate, gate_act="hardsigmoid"):
     """-> (dz, dgate) of :func:`se_scale_fwd` in one pass over ``dout`` and ``z``; dgate has
     gate's shape and dtype."""
     if use_native(dout):
-        return native().se_scale_bwd(dout, z, gate)
-    return _ref.se_scale_bwd(dout, z, gate)
+        return native().se_scale_bwd(dout, z, gate, _se_gate(gate_act))
+    return _ref.se_scale_bwd(dout, z, gate, gate_act)

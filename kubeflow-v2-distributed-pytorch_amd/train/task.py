@@ -284,8 +284,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--label-smoothing", type=float, default=0.0,
                    help="label smoothing of the training loss")
     p.add_argument("--stochastic-depth", type=float, default=None, metavar="P",
-                   help="stochastic depth of the convnext_* / swin_* models (default: the family's own "
-                        "value, e.g. 0.1 for convnext_tiny)")
+                   help="stochastic depth of the convnext_* / swin_* / efficientnet_* models (default: "
+                        "the family's own value, e.g. 0.1 for convnext_tiny)")
     p.add_argument("--mixup-alpha", type=float, default=0.0,
                    help="Mixup: lambda ~ Beta(a, a); 0 = off")
     p.add_argument("--cutmix-alpha", type=float, default=0.0,
@@ -548,11 +548,16 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
         kw["in_chans"] = C
         kw["stochastic_depth_prob"] = args.stochastic_depth
         kw["seed"] = args.random_seed
+    elif args.arch.startswith("efficientnet_"):
+        if args.stochastic_depth is not None and not 0.0 <= args.stochastic_depth < 1.0:
+            raise SystemExit(f"--stochastic-depth must be in [0, 1), got {args.stochastic_depth}")
+        kw["stochastic_depth_prob"] = args.stochastic_depth
+        kw["seed"] = args.random_seed
     elif args.stochastic_depth is not None:
-        raise SystemExit(f"--stochastic-depth applies to the swin_* and convnext_* models only, "
-                         f"not to --arch {args.arch}")
+        raise SystemExit(f"--stochastic-depth applies to the efficientnet_*, swin_* and convnext_* "
+                         f"models only, not to --arch {args.arch}")
     model = create_model(args.arch, **kw)
-    if args.arch.startswith(("convnext_", "swin_")):
+    if args.arch.startswith(("convnext_", "swin_", "efficientnet_")):
         stochastic_depth = model.stochastic_depth_prob
         print(f"=> {args.arch}: stochastic depth {stochastic_depth:g}", flush=True)
     if args.pretrained:
