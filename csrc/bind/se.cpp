@@ -45,8 +45,8 @@ const float* opt_vec_ptr(const optional<Tensor>& t, int64_t n, const Tensor& ref
 }
 int check_se_act(int64_t act) {
   TORCH_CHECK(act == mipipe::kSeActRelu || act == mipipe::kSeActHardswish ||
-                  act == mipipe::kSeActSilu,
-              "act must be SE_ACT_RELU, SE_ACT_HARDSWISH or SE_ACT_SILU, got ", act);
+                  act == mipipe::kSeActSilu || act == mipipe::kSeActGelu,
+              "act must be SE_ACT_RELU, SE_ACT_HARDSWISH, SE_ACT_SILU or 5 (GELU), got ", act);
   return (int)act;
 }
 int check_gate_act(int64_t ga) {

@@ -2058,6 +2058,7 @@ void bind_convnext(py::module& m);  // csrc/bind/convnext.cpp: dwconv7, scale_re
 void bind_se(py::module& m);    // csrc/bind/se.cpp: bn_act_pool, se_scale
 void bind_dwconvk(py::module& m);  // csrc/bind/dwconvk.cpp: depthwise 3x3 / 5x5, stride 1 / 2
 void bind_swin(py::module& m);  // csrc/bind/swin.cpp: window attention, patch_merge
+void bind_maxvit(py::module& m);  // csrc/bind/maxvit.cpp: block / grid partition attention
 }
 
 namespace mipipe_comm {
@@ -2076,6 +2077,7 @@ PYBIND11_MODULE(_C, m) {
   mipipe_bind::bind_se(m);
   mipipe_bind::bind_dwconvk(m);
   mipipe_bind::bind_swin(m);
+  mipipe_bind::bind_maxvit(m);
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
         py::arg("shift") = py::none(), py::arg("slab_sum") = py::none(),
         py::arg("slab_sq") = py::none(), py::arg("bias") = py::none(), py::arg("relu") = false,

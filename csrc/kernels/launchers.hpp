@@ -394,6 +394,7 @@ constexpr int kSeReduceBlocks = 1024;
 constexpr int kSeActRelu = 1;       // vision.hip's code
 constexpr int kSeActHardswish = 3;
 constexpr int kSeActSilu = 4;       // u * sigmoid(u), sigmoid through expf (not bit-exact to _ref)
+constexpr int kSeActGelu = 5;       // u * Φ(u), exact (erf) form through one expf (likewise)
 constexpr int kSeGateHardsigmoid = 0;
 constexpr int kSeGateSigmoid = 1;
 struct SeSlices {
@@ -573,6 +574,16 @@ void winattn8_fwd(const void* qkv, const float* bias, const float* logit_scale, 
 void winattn8_bwd(const void* dout, const void* qkv, const float* bias, const float* logit_scale,
                   void* dqkv, float* partial, float* dbias, float* dlogit_scale, int B, int Hs,
                   int Ws, int H, int sy, int sx, hipStream_t st);
+// MaxViT: block / grid partition attention with a relative-position table (relattn.hip, on the
+// frame at WS = 7), head width 32, bf16: qkv / o / table as winattn_fwd's; grid = false: the
+// contiguous 7x7 windows; grid = true: window (a, b') of a sample holds the 49 tokens (gy*Hs/7 +
+// a, gx*Ws/7 + b'); scores = softmax(q·kᵀ·scale + table[rel]); Hs % 7 == Ws % 7 == 0.
+void relattn_fwd(const void* qkv, const float* table, void* o, int B, int Hs, int Ws, int H,
+                 bool grid, float scale, hipStream_t st);
+// dqkv / dtable / partial as winattn_bwd's
+void relattn_bwd(const void* dout, const void* qkv, const float* table, void* dqkv,
+                 float* partial, float* dtable, int B, int Hs, int Ws, int H, bool grid,
+                 float scale, hipStream_t st);
 // PatchMerging's gather: x [B, Hs, Ws, C] -> out [B*Hs/2*Ws/2, 4C], column groups (0::2, 0::2),
 // (1::2, 0::2), (0::2, 1::2), (1::2, 1::2); bwd: the inverse permutation (in = dy, out = dx).
 // bf16, C % 8 == 0, even Hs and Ws.

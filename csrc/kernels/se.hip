@@ -6,8 +6,8 @@
 // accesses; geometry: launchers.hpp (se_slices).  Every elementwise result is a fixed sequence of
 // rounded fp32 operations (contraction off: ops/_ref.py reproduces them bit for bit), every sum
 // a fixed-order sum of per-block partial rows: the same bits on every launch, in every mode.
-// The SiLU / sigmoid variants go through expf: a fixed sequence too, but not the bits of
-// ops/_ref.py (tested against float64 within a bound).
+// The SiLU / sigmoid / GELU (MaxViT's MBConv) variants go through expf: a fixed sequence too, but
+// not the bits of ops/_ref.py (tested against float64 within a bound).
 #include "common.hpp"
 #include "launchers.hpp"
 
@@ -16,7 +16,8 @@
 namespace mipipe {
 namespace {
 
-constexpr int kRelu = kSeActRelu, kHswish = kSeActHardswish, kSilu = kSeActSilu;
+constexpr int kRelu = kSeActRelu, kHswish = kSeActHardswish, kSilu = kSeActSilu,
+              kGelu = kSeActGelu;
 constexpr int U = kSeRowU;
 constexpr int kRedFloats = kSeThreads * 8;  // one [rpb][tpr * 8] array of block partials
 
@@ -108,10 +109,33 @@ __device__ __forceinline__ float se_affine(float y, float sc, float bi) {
 }
 // the logistic sigmoid through expf: exp(-v) overflowing to inf gives 1 / inf = 0, never a NaN
 __device__ __forceinline__ float se_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
+// The exact (erf) GELU's two pieces from ONE expf and one division: cdf = Φ(u) through
+// erfc(|u|/√2) = poly(t)·exp(-u²/2), t = 1 / (1 + p|u|/√2) (Abramowitz & Stegun 7.1.26, |error|
+// of erf <= 1.5e-7, so of Φ <= 7.5e-8 before the fp32 roundings), pdf = φ(u) from the same
+// exponential.  misc.hip's gelu_grad uses the same expansion with the fast-math intrinsics;
+// here it is a fixed sequence of rounded operations like the rest of this file.
+struct SeGelu {
+  float cdf, pdf;
+};
+__device__ __forceinline__ SeGelu se_gelu_parts(float u) {
+  const float e = expf((-0.5f * u) * u);
+  const float t = 1.f / (1.f + 0.23164189f * fabsf(u));  // p / √2, p = 0.3275911
+  float poly = 1.061405429f * t + -1.453152027f;
+  poly = poly * t + 1.421413741f;
+  poly = poly * t + -0.284496736f;
+  poly = poly * t + 0.254829592f;
+  const float half_erfc = (0.5f * (poly * t)) * e;  // Φ(-|u|)
+  SeGelu g;
+  g.cdf = u >= 0.f ? 1.f - half_erfc : half_erfc;
+  g.pdf = 0.3989422804014327f * e;
+  return g;
+}
 template <int ACT>
 __device__ __forceinline__ float se_act(float u) {
   if constexpr (ACT == kRelu) {
     return fmaxf(u, 0.f);
+  } else if constexpr (ACT == kGelu) {
+    return u * se_gelu_parts(u).cdf;
   } else if constexpr (ACT == kSilu) {
     return u * se_sigmoid(u);
   } else {
@@ -121,11 +145,14 @@ __device__ __forceinline__ float se_act(float u) {
 }
 // e * act'(u) by torch's rules at the knees: ReLU passes u > 0; Hardswish is 0 for u <= -3, the
 // slope (u / 3) + 0.5 inside (-3, 3) and 1 for u >= 3 (what ATen's hardswish_backward returns);
-// SiLU is e * (s * (1 + u * (1 - s))), s = sigmoid(u)
+// SiLU is e * (s * (1 + u * (1 - s))), s = sigmoid(u); GELU is e * (Φ(u) + u φ(u))
 template <int ACT>
 __device__ __forceinline__ float se_act_grad(float u, float e) {
   if constexpr (ACT == kRelu) {
     return u > 0.f ? e : 0.f;
+  } else if constexpr (ACT == kGelu) {  // e * (Φ(u) + u φ(u))
+    const SeGelu g = se_gelu_parts(u);
+    return e * (g.cdf + u * g.pdf);
   } else if constexpr (ACT == kSilu) {
     const float sg = se_sigmoid(u);
     const float t = u * (1.f - sg);
@@ -447,7 +474,8 @@ inline dim3 se_grid(const SeGeom& g, int cap) {
   return dim3(std::min<uint32_t>(g.units, (uint32_t)cap), (g.C8 + kSeThreads - 1) / kSeThreads);
 }
 inline int finish_grid(long n) { return (int)std::min<long>((n + 255) / 256, kSeMaxBlocks); }
-inline bool se_act_ok(int act) { return act == kRelu || act == kHswish || act == kSilu; }
+inline bool se_act_ok(int act) { return act == kRelu || act == kHswish || act == kSilu || act == kGelu;
+}
 
 }  // namespace
 
@@ -457,7 +485,7 @@ void bn_act_pool_fwd(const void* y, const float* scale, const float* bias, void*
   const SeGeom g = se_geom(N, HW, C);
   dispatch_act(f32, [&](auto t) {
     using T = decltype(t);
-    dispatch_int<kRelu, kHswish, kSilu>(act, [&](auto a) {
+    dispatch_int<kRelu, kHswish, kSilu, kGelu>(act, [&](auto a) {
       dispatch_bool(pm != nullptr, [&](auto p) {
         hipLaunchKernelGGL((bn_act_pool_fwd_kernel<T, decltype(a)::value, decltype(p)::value>),
                            se_grid(g, kSeMaxBlocks), dim3(kSeThreads), 0, st, (const T*)y, scale,
@@ -480,7 +508,7 @@ void bn_act_pool_bwd_reduce(const void* dz, const void* y, const float* scale, c
   float* ws_gx = ws + (long)P * C;
   dispatch_act(f32, [&](auto t) {
     using T = decltype(t);
-    dispatch_int<kRelu, kHswish, kSilu>(act, [&](auto a) {
+    dispatch_int<kRelu, kHswish, kSilu, kGelu>(act, [&](auto a) {
       dispatch_bool(dpm != nullptr, [&](auto d) {
         hipLaunchKernelGGL(
             (bn_act_pool_bwd_reduce_kernel<T, decltype(a)::value, decltype(d)::value>),
@@ -501,7 +529,7 @@ void bn_act_pool_bwd_apply(const void* dz, const void* y, const float* scale, co
   const float inv_cnt = (float)(1.0 / ((double)N * (double)HW));
   dispatch_act(f32, [&](auto t) {
     using T = decltype(t);
-    dispatch_int<kRelu, kHswish, kSilu>(act, [&](auto a) {
+    dispatch_int<kRelu, kHswish, kSilu, kGelu>(act, [&](auto a) {
       dispatch_bool(dpm != nullptr, [&](auto d) {
         dispatch_bool(sum_g != nullptr, [&](auto s) {
           hipLaunchKernelGGL((bn_act_pool_bwd_apply_kernel<T, decltype(a)::value,

@@ -599,6 +599,63 @@ def window_attention(qkv: Tensor, table: Tensor, B: int, Hs: int, Ws: int, heads
     return of, dqkv.reshape(B * Hs * Ws, 3 * heads * D).to(qkv.dtype), dtable
 
 
+# ---- MaxViT: block / grid partition attention (csrc/kernels/relattn.hip)
+def partition_index(Hs: int, Ws: int, mode: str, device="cpu") -> Tensor:
+    """idx [nW, 49]: the row (inside a sample, NHWC order) of token n = 7y + x of partition w.
+    ``block``: w = wy*(Ws/7) + wx holds (wy*7 + y, wx*7 + x).  ``grid``: w = a*(Ws/7) + b' holds
+    (y*(Hs/7) + a, x*(Ws/7) + b'), the dilated partition."""
+    if mode not in ("block", "grid"):
+        raise ValueError(f"partition_attention: mode must be 'block' or 'grid', got {mode!r}")
+    if Hs % WIN or Ws % WIN or Hs < WIN or Ws < WIN:
+        raise ValueError(f"the map {Hs}x{Ws} is not a whole number of {WIN}x{WIN} partitions")
+    t = (torch.arange(Hs, device=device)[:, None] * Ws + torch.arange(Ws, device=device)[None, :])
+    if mode == "block":
+        t = t.reshape(Hs // WIN, WIN, Ws // WIN, WIN).permute(0, 2, 1, 3)
+    else:
+        t = t.reshape(WIN, Hs // WIN, WIN, Ws // WIN).permute(1, 3, 0, 2)
+    return t.reshape(-1, WIN * WIN)
+
+
+def partition_attention(qkv: Tensor, table: Tensor, B: int, Hs: int, Ws: int, heads: int,
+                        mode: str, scale: float, do: Optional[Tensor] = None):
+    """MaxViT's relative attention on the packed projection: qkv [B*Hs*Ws, 3*heads*32] (q | k | v,
+    head-major, NHWC token order), table [169, heads] -> o [B*Hs*Ws, heads*32]; per partition
+    (:func:`partition_index`) and head ``P = softmax(q kᵀ scale + table[rel])``, ``o = P v``:
+    partition, matmul, softmax, departition.  With ``do`` also the closed-form backward: returns
+    (o, dqkv, dtable).  fp32 (fp64 for fp64 input)."""
+    idx = partition_index(Hs, Ws, mode, qkv.device)
+    rel = window_geometry(WIN, WIN, 0, qkv.device)[1]
+    nW, N, D = idx.shape[0], WIN * WIN, WIN_HEAD
+    if qkv.shape != (B * Hs * Ws, 3 * heads * D):
+        raise ValueError(f"qkv must be [{B * Hs * Ws}, {3 * heads * D}], got {tuple(qkv.shape)}")
+    if tuple(table.shape) != (169, heads):
+        raise ValueError(f"table must be [169, {heads}], got {tuple(table.shape)}")
+    tab = _f(table)
+    x = _f(qkv).reshape(B, Hs * Ws, 3, heads, D)[:, idx]  # [B, nW, 49, 3, h, D]
+    q, k, v = (x[:, :, :, i].transpose(2, 3) for i in range(3))  # [B, nW, h, 49, D]
+    p = torch.softmax(q @ k.transpose(-1, -2) * scale + tab[rel].permute(2, 0, 1), -1)
+    o = p @ v
+
+    def rows(t, out):  # [B, nW, h, 49, D] -> its tokens' rows of out [B, Hs*Ws, h, D]
+        out[:, idx.reshape(-1)] = t.transpose(2, 3).reshape(B, nW * N, heads, D)
+        return out
+
+    of = rows(o, torch.empty(B, Hs * Ws, heads, D, dtype=o.dtype, device=o.device))
+    of = of.reshape(B * Hs * Ws, heads * D).to(qkv.dtype)
+    if do is None:
+        return of
+    dof = _f(do).reshape(B, Hs * Ws, heads, D)[:, idx].transpose(2, 3)
+    dv = p.transpose(-1, -2) @ dof
+    ds = p * (dof @ v.transpose(-1, -2) - (dof * o).sum(-1, keepdim=True))
+    dq, dk = ds @ k * scale, ds.transpose(-1, -2) @ q * scale
+    dqkv = torch.empty(B, Hs * Ws, 3, heads, D, dtype=o.dtype, device=o.device)
+    for i, t in enumerate((dq, dk, dv)):
+        rows(t, dqkv[:, :, i])
+    dtable = torch.zeros_like(tab).index_add_(
+        0, rel.reshape(-1), ds.sum((0, 1)).permute(1, 2, 0).reshape(N * N, heads))
+    return of, dqkv.reshape(B * Hs * Ws, 3 * heads * D).to(qkv.dtype), dtable
+
+
 WIN8 = 8                    # Swin V2's window side
 LOGIT_SCALE_MAX = math.log(100.0)
 NORM_EPS = 1e-12            # F.normalize's
@@ -1266,16 +1323,23 @@ def sigmoid(v: Tensor) -> Tensor:
     return 1.0 / (1.0 + torch.exp(-v))
 
 
+_SQRT_HALF = 0.7071067811865476
+_INV_SQRT_2PI = 0.3989422804014327
+
+
 def se_act(u: Tensor, act: str) -> Tensor:
     """relu: max(u, 0); hardswish: (u * clamp(u + 3, 0, 6)) / 6 with a true division; silu:
-    u * sigmoid(u)."""
+    u * sigmoid(u); gelu: u * Φ(u) through erf (the kernels use a one-exponential expansion of
+    erfc: they agree to a bound, not bit for bit)."""
     if act == "relu":
         return torch.relu(u)
     if act == "hardswish":
         return (u * (u + 3.0).clamp(0.0, 6.0)) / _const(6.0, u)
     if act == "silu":
         return u * sigmoid(u)
-    raise ValueError(f"bn_act_pool: act must be relu, hardswish or silu, got {act!r}")
+    if act == "gelu":  # the exact (erf) form, nn.GELU()'s
+        return u * (0.5 * (1.0 + torch.erf(u * _SQRT_HALF)))
+    raise ValueError(f"bn_act_pool: act must be relu, hardswish, silu or gelu, got {act!r}")
 
 
 def se_act_grad(u: Tensor, e: Tensor, act: str) -> Tensor:
@@ -1291,7 +1355,10 @@ def se_act_grad(u: Tensor, e: Tensor, act: str) -> Tensor:
     if act == "hardswish":
         mid = e * ((u / _const(3.0, u)) + 0.5)
         return torch.where(u <= -3.0, zero, torch.where(u < 3.0, mid, e))
-    raise ValueError(f"bn_act_pool: act must be relu, hardswish or silu, got {act!r}")
+    if act == "gelu":  # e * (Φ(u) + u φ(u))
+        cdf = 0.5 * (1.0 + torch.erf(u * _SQRT_HALF))
+        return e * (cdf + u * (torch.exp(-0.5 * u * u) * _INV_SQRT_2PI))
+    raise ValueError(f"bn_act_pool: act must be relu, hardswish, silu or gelu, got {act!r}")
 
 
 def hardsigmoid(gate: Tensor) -> Tensor:

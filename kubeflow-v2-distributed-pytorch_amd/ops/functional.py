@@ -1519,7 +1519,7 @@ class _BNActPoolFn(Function):
 def bn_act_pool(y: Tensor, st: BNStats, bn, act: str, pool: bool = False):
     """``(z, pm)``: z = act(BatchNorm(y)) for NHWC ``y`` with the statistics ``st`` (of the MFMA
     conv epilogue, or :func:`K.chan_stats` + :func:`bn_stats_from_partials`), act in {relu,
-    hardswish, silu}; with ``pool`` also pm [N, C] fp32, the mean of z over (h, w) — the
+    hardswish, silu, gelu}; with ``pool`` also pm [N, C] fp32, the mean of z over (h, w) — the
     squeeze-excitation block's squeeze — else None.  The backward takes both gradients and makes
     a single reduce + apply pair: the pool's backward is an addend inside them."""
     return _BNActPoolFn.apply(y.contiguous(), bn.weight, bn.bias, st, act, bool(pool))
@@ -1659,6 +1659,43 @@ def window_attention(qkv: Tensor, table: Tensor, batch: int, hs: int, ws: int, h
     flat gradient buffer when the parameter lives in one."""
     return _WindowAttentionFn.apply(qkv.contiguous(), table, int(batch), int(hs), int(ws),
                                     int(heads), shift)
+
+
+class _PartitionAttentionFn(Function):
+    @staticmethod
+    def forward(ctx, qkv, table, B, Hs, Ws, heads, mode, scale):
+        ctx.save_for_backward(qkv)
+        ctx.table, ctx.cfg = table, (B, Hs, Ws, heads, mode, scale)
+        return K.partition_attention_fwd(qkv, table.detach(), B, Hs, Ws, heads, mode, scale)
+
+    @staticmethod
+    def backward(ctx, do):
+        (qkv,) = ctx.saved_tensors
+        table = ctx.table
+        do = do.contiguous()
+        tt = _direct_grad_target(table) if K.use_native(do) and ctx.needs_input_grad[1] else None
+        dqkv, dt = K.partition_attention_bwd(do, qkv, table.detach(), *ctx.cfg,
+                                             dtable=None if tt is None else tt[1].reshape(-1))
+        if tt is not None:
+            tt[0].grad_ready(table)
+        elif dt is not None:
+            dt = dt.reshape(table.shape).to(table.dtype) if ctx.needs_input_grad[1] else None
+        return dqkv, dt, None, None, None, None, None, None
+
+
+def partition_attention(qkv: Tensor, table: Tensor, batch: int, hs: int, ws: int, heads: int,
+                        mode: str, scale: float) -> Tensor:
+    """MaxViT's relative attention over the packed QKV projection output, one kernel each way:
+    qkv [B*Hs*Ws, 3*heads*32] (rows in NHWC token order; q | k | v, head-major), ``table`` the fp32
+    ``relative_position_bias_table`` parameter [169, heads], ``mode`` "block" (7x7 windows) or
+    "grid" (the dilated partition), ``scale`` the score scale -> o [B*Hs*Ws, heads*32].  Both
+    partitions and their inverses are address arithmetic inside the kernels; the backward
+    recomputes the probabilities and sums the table's gradient in a fixed order, straight into the
+    flat gradient buffer when the parameter lives in one."""
+    if mode not in ("block", "grid"):
+        raise ValueError(f"partition_attention: mode must be 'block' or 'grid', got {mode!r}")
+    return _PartitionAttentionFn.apply(qkv.contiguous(), table, int(batch), int(hs), int(ws),
+                                       int(heads), mode, float(scale))
 
 
 class _WindowAttentionV2Fn(Function):

@@ -32,7 +32,8 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "scale_residual_fwd", "scale_residual_bwd",
            "bn_act_pool_fwd", "bn_act_pool_bwd_reduce", "bn_act_pool_bwd_apply", "se_scale_fwd",
            "se_scale_bwd", "window_attention_fwd", "window_attention_bwd", "patch_merge",
-           "window_attention_v2_fwd", "window_attention_v2_bwd"]
+           "window_attention_v2_fwd", "window_attention_v2_bwd",
+           "partition_attention_fwd", "partition_attention_bwd"]
 
 _ALLOW_REF_ON_GPU = os.environ.get("MIPIPE_ALLOW_REF_ON_GPU", "0") == "1"
 
@@ -606,6 +607,32 @@ def window_attention_bwd(do, qkv, table, B, Hs, Ws, heads, shift, dtable=None):
     return dqkv, g
 
 
+# ----------------------------------------------------------------------------- relattn.hip
+def partition_attention_fwd(qkv, table, B, Hs, Ws, heads, mode, scale):
+    """MaxViT's relative attention over 49-token partitions (head width 32): qkv and ``table`` as
+    :func:`window_attention_fwd`, ``mode`` "block" (contiguous 7x7 windows) or "grid" (the dilated
+    partition: tokens Hs/7 rows and Ws/7 pixels apart), ``scale`` the score scale (MaxViT's is
+    C^-1/2 of the whole width) -> o [B*Hs*Ws, heads*32] (:func:`_ref.partition_attention`).
+    Native: bf16."""
+    if use_native(qkv):
+        return native().relattn_fwd(qkv, table, int(B), int(Hs), int(Ws), int(heads), str(mode),
+                                    float(scale))
+    return _ref.partition_attention(qkv, table, B, Hs, Ws, heads, mode, scale)
+
+
+def partition_attention_bwd(do, qkv, table, B, Hs, Ws, heads, mode, scale, dtable=None):
+    """-> (dqkv, dtable): as :func:`window_attention_bwd` (fixed-order table gradient,
+    ACCUMULATED into ``dtable`` when given)."""
+    if use_native(do):
+        return native().relattn_bwd(do, qkv, table, int(B), int(Hs), int(Ws), int(heads),
+                                    str(mode), float(scale), dtable)
+    _, dqkv, g = _ref.partition_attention(qkv, table, B, Hs, Ws, heads, mode, scale, do)
+    if dtable is not None:
+        dtable.add_(g.reshape(dtable.shape).to(dtable.dtype))
+        g = None
+    return dqkv, g
+
+
 # ----------------------------------------------------------------------------- winattn8.hip
 def window_attention_v2_fwd(qkv, bias, logit_scale, B, Hs, Ws, heads, shift):
     """Swin V2's shifted-window cosine attention (8x8 windows, head width 32): qkv as
@@ -1031,13 +1058,14 @@ def scale_residual_bwd(dout, f, gamma, hw, p=0.0, seed=0, dgamma=None, dbias=Non
 
 
 # ----------------------------------------------------------------------------- se.hip
-_SE_ACT = {"relu": 1, "hardswish": 3, "silu": 4}  # SE_ACT_RELU, SE_ACT_HARDSWISH, SE_ACT_SILU
+# SE_ACT_RELU, SE_ACT_HARDSWISH, SE_ACT_SILU, kSeActGelu
+_SE_ACT = {"relu": 1, "hardswish": 3, "silu": 4, "gelu": 5}
 _SE_GATE = {"hardsigmoid": 0, "sigmoid": 1}  # SE_GATE_HARDSIGMOID, SE_GATE_SIGMOID
 
 
 def _se_act(act: str) -> int:
     if act not in _SE_ACT:
-        raise ValueError(f"bn_act_pool: act must be relu, hardswish or silu, got {act!r}")
+        raise ValueError(f"bn_act_pool: act must be relu, hardswish, silu or gelu, got {act!r}")
     return _SE_ACT[act]
 
 

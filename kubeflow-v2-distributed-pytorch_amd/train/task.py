@@ -553,11 +553,20 @@ def main_worker(gpu, ngpus_per_node, args) -> dict:
             raise SystemExit(f"--stochastic-depth must be in [0, 1), got {args.stochastic_depth}")
         kw["stochastic_depth_prob"] = args.stochastic_depth
         kw["seed"] = args.random_seed
+    elif args.arch.startswith("maxvit_"):
+        unit = 56 if args.arch.endswith("_nano") else 224
+        if H != W or H % unit:
+            raise SystemExit(f"--arch {args.arch} needs square images whose side is a multiple of "
+                             f"{unit} (7x7 partitions at every stage; no padding), got {H}x{W}")
+        if args.stochastic_depth is not None and not 0.0 <= args.stochastic_depth < 1.0:
+            raise SystemExit(f"--stochastic-depth must be in [0, 1), got {args.stochastic_depth}")
+        kw["stochastic_depth_prob"] = args.stochastic_depth
+        kw["seed"] = args.random_seed
     elif args.stochastic_depth is not None:
         raise SystemExit(f"--stochastic-depth applies to the efficientnet_*, swin_* and convnext_* "
                          f"models only, not to --arch {args.arch}")
     model = create_model(args.arch, **kw)
-    if args.arch.startswith(("convnext_", "swin_", "efficientnet_")):
+    if args.arch.startswith(("convnext_", "swin_", "efficientnet_", "maxvit_")):
         stochastic_depth = model.stochastic_depth_prob
         print(f"=> {args.arch}: stochastic depth {stochastic_depth:g}", flush=True)
     if args.pretrained:

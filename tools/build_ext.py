@@ -36,7 +36,7 @@ EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 
 # kernel files compiled without the packed fp32 VALU forms (v_pk_add / mul / fma_f32)
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-_NO_PACKED_FP32_FILES = {"winattn.hip", "winattn8.hip"}
+_NO_PACKED_FP32_FILES = {"winattn.hip", "winattn8.hip", "relattn.hip"}
 
 
 def _newest_header() -> float:
