@@ -2057,6 +2057,7 @@ void bind_vit(py::module& m);   // csrc/bind/vit.cpp: patchify, token assembly
 void bind_convnext(py::module& m);  // csrc/bind/convnext.cpp: dwconv7, scale_residual
 void bind_se(py::module& m);    // csrc/bind/se.cpp: bn_act_pool, se_scale
 void bind_dwconvk(py::module& m);  // csrc/bind/dwconvk.cpp: depthwise 3x3 / 5x5, stride 1 / 2
+void bind_gconv3(py::module& m);  // csrc/bind/gconv3.cpp: grouped 3x3 on MFMA, group width 8 ... 64
 void bind_swin(py::module& m);  // csrc/bind/swin.cpp: window attention, patch_merge
 void bind_maxvit(py::module& m);  // csrc/bind/maxvit.cpp: block / grid partition attention
 }
@@ -2076,6 +2077,7 @@ PYBIND11_MODULE(_C, m) {
   mipipe_bind::bind_convnext(m);
   mipipe_bind::bind_se(m);
   mipipe_bind::bind_dwconvk(m);
+  mipipe_bind::bind_gconv3(m);
   mipipe_bind::bind_swin(m);
   mipipe_bind::bind_maxvit(m);
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),

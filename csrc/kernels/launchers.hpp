@@ -496,6 +496,54 @@ void dwconvk_dgrad(const void* dy, const void* w, const void* addend, void* dx, 
 void dwconvk_wgrad(const void* dy, const void* x, float* ws, float* dw, int N, int H, int W, int C,
                    int k, int s, bool f32, hipStream_t st);
 
+// ---- grouped 3 x 3 on MFMA, group width G = C / groups in {8, 16 ... 64}, pad 1, stride 1 / 2,
+// NHWC bf16 (gconv3.hip).  Forward / weight-grad: a block owns a gc3_tile_h x gc3_tile_w OUTPUT
+// tile of one channel block (gc3_groups_per_block(G) whole groups, at most 64 channels) with the
+// input halo and its weight rows in LDS.  Stride-2 data-grad: a kGc3DgradTile^2 tile of dx, one
+// GEMM per parity class.  Channel blocks in grid.y, tiles grid-strided past kGc3MaxBlocks.
+constexpr int kGc3MaxBlocks = 2048;
+constexpr int kGc3DgradTile = 16;
+constexpr int kGc3WgradBlocks = 1024;
+constexpr int kGc3WgradMinRows = 16;
+constexpr int kGc3WgradMaxRows = 512;
+inline bool gc3_supported(int C, int G, int s) {
+  return G >= 8 && G <= 64 && G % 8 == 0 && C > 0 && C % G == 0 && (s == 1 || s == 2);
+}
+constexpr int gc3_groups_per_block(int G) { return 64 / G; }
+inline int gc3_tile_h(int) { return 8; }
+inline int gc3_tile_w(int s) { return s == 1 ? 16 : 8; }
+inline int gc3_out(int L, int s) { return (L - 1) / s + 1; }
+inline long gc3_tiles(int N, int Ho, int Wo, int s) {
+  const int th = gc3_tile_h(s), tw = gc3_tile_w(s);
+  return (long)N * ((Ho + th - 1) / th) * ((Wo + tw - 1) / tw);
+}
+// partial rows of the fused BatchNorm statistics: one per forward block of a channel block
+inline int gc3_stat_rows(int N, int Ho, int Wo, int s) {
+  const long t = gc3_tiles(N, Ho, Wo, s);
+  return (int)(t < kGc3MaxBlocks ? t : kGc3MaxBlocks);
+}
+// weight-grad partial slabs: kGc3WgradBlocks / channel blocks, in [kGc3WgradMinRows,
+// kGc3WgradMaxRows] and at most the number of tiles
+inline int gc3_wgrad_rows(int N, int Ho, int Wo, int C, int G, int s) {
+  const int cb = gc3_groups_per_block(G) * G;
+  long p = kGc3WgradBlocks / ((C + cb - 1) / cb);
+  if (p < kGc3WgradMinRows) p = kGc3WgradMinRows;
+  if (p > kGc3WgradMaxRows) p = kGc3WgradMaxRows;
+  const long t = gc3_tiles(N, Ho, Wo, s);
+  return (int)(p < t ? p : t);
+}
+// y [N, Ho, Wo, C] = bf16(grouped conv(x, w)), w [C, 3, 3, G].  shift != null: also the shifted
+// sums of the STORED y through ws ([2][gc3_stat_rows][C] partial rows, scratch) -> ps, pss [C].
+void gconv3_fwd(const void* x, const void* w, const float* shift, void* y, float* ws, float* ps,
+                float* pss, int N, int H, int W, int C, int G, int s, hipStream_t st);
+// dx [N, H, W, C] = bf16(data-grad of dy [N, Ho, Wo, C] (+ addend, fp32, before the rounding))
+void gconv3_dgrad(const void* dy, const void* w, const void* addend, void* dx, int N, int H, int W,
+                  int C, int G, int s, hipStream_t st);
+// dw [C, G, 3, 3] fp32 (channels_last: stored as [C, 3, 3, G]) += sum dy * x through ws
+// ([gc3_wgrad_rows][C * G * 9] slabs in dw's order, scratch)
+void gconv3_wgrad(const void* dy, const void* x, float* ws, float* dw, int N, int H, int W, int C,
+                  int G, int s, bool channels_last, hipStream_t st);
+
 // ---- loss / data ------------------------------------------------------------------------------
 // Launch constants of loss.hip, exported to Python (CE_* / TOP1_*) so that the edge tests derive
 // their shapes from the values the kernels use.  Cross-entropy: blocks of kCeThreads threads, one

@@ -28,7 +28,7 @@ def register_model(name: str, fn: Callable) -> None:
 
 
 _ZOO_MODULES = ("vgg", "mobilenet", "shufflenet", "squeezenet", "densenet", "inception", "bert", "vit",
-                "convnext", "mobilenetv3", "swin", "swin_v2", "efficientnet", "maxvit")
+                "convnext", "mobilenetv3", "swin", "swin_v2", "efficientnet", "maxvit", "regnet")
 
 
 def _lazy_register():

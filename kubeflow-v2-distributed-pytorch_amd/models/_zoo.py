@@ -23,6 +23,7 @@ from mipipe.ops import kernels as K
 
 __all__ = ["ZooModel", "Exec", "run_seq", "run_module", "conv_bn", "conv_bn_act_pool",
            "dwconv_bn_act_pool", "dwconvk_route", "DWCONVK_OLD_ROUTE", "act_of",
+           "gconv_bn_act_pool", "gconv3_route", "GCONV3_OLD_ROUTE",
            "global_pool",
            "adaptive_avg_pool", "ref_linear"]
 
@@ -105,6 +106,40 @@ def dwconv_bn_act_pool(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, 
         return conv_bn_act_pool(x, conv, bn, act, pool)
     y, ps, pss = MF.dwconvk(x, conv.weight, conv.compute_weight(x.dtype), conv.stride[0],
                             bn.running_mean if bn.training else None, res_give)
+    st = MF.bn_stats_from_partials(ps, pss, y.numel() // y.shape[-1], bn, bn.training)
+    return MF.bn_act_pool(y, st, bn, act, pool)
+
+
+#: Grouped 3x3 shapes (group width, stride, channels, input rows) at which tools/regnet_bench.py
+#: did not see the MFMA kernels of gconv3.hip ahead of the route ``XConv2d.run`` takes
+#: (block_group_conv2d or gconv, + chan_stats) in every alternation: :func:`gconv_bn_act_pool`
+#: sends them through the old route.
+GCONV3_OLD_ROUTE: frozenset = frozenset()
+
+
+def gconv3_route(x: torch.Tensor, conv: mnn.XConv2d) -> bool:
+    """Whether :func:`gconv_bn_act_pool` runs ``conv`` on NHWC ``x`` through ``MF.gconv3``: bf16
+    on the GPU, a bias-free 3x3 with pad 1 at stride 1 / 2, dilation 1, as many output as input
+    channels, a group width G = C / groups with G % 8 == 0 and G <= 64, at a shape that is not in
+    :data:`GCONV3_OLD_ROUTE`."""
+    C, s = x.shape[-1], conv.stride[0]
+    G = C // conv.groups
+    return (x.is_cuda and x.dtype == torch.bfloat16 and conv.in_channels == C == conv.out_channels
+            and conv.bias is None and conv.kernel_size == (3, 3) and conv.stride == (s, s)
+            and s in (1, 2) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+            and conv.padding_mode == "zeros" and C % conv.groups == 0 and G % 8 == 0
+            and 8 <= G <= 64 and (G, s, C, x.shape[1]) not in GCONV3_OLD_ROUTE)
+
+
+def gconv_bn_act_pool(x: torch.Tensor, conv: mnn.XConv2d, bn: tnn.BatchNorm2d, act: str,
+                      pool: bool = False):
+    """:func:`conv_bn_act_pool` for a grouped 3x3 conv: where :func:`gconv3_route` holds,
+    ``MF.gconv3`` (MFMA kernel, the BatchNorm statistics from the same pass) and then
+    ``MF.bn_act_pool``; elsewhere the generic route."""
+    if not gconv3_route(x, conv):
+        return conv_bn_act_pool(x, conv, bn, act, pool)
+    y, ps, pss = MF.gconv3(x, conv.weight, conv.compute_weight(x.dtype), conv.stride[0],
+                           bn.running_mean if bn.training else None)
     st = MF.bn_stats_from_partials(ps, pss, y.numel() // y.shape[-1], bn, bn.training)
     return MF.bn_act_pool(y, st, bn, act, pool)
 

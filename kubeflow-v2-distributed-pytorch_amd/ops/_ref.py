@@ -1251,6 +1251,47 @@ def dwconvk_wgrad(dy: Tensor, x: Tensor, k: int, stride: int) -> Tensor:
                                        stride=int(stride), padding=(k - 1) // 2, groups=C)
 
 
+# ---- grouped 3 x 3, group width 8 ... 64, stride 1 / 2 (csrc/kernels/gconv3.hip)
+def _gc3_args(w: Tensor, C: int, stride: int) -> int:
+    G = int(w.shape[-1])
+    if tuple(w.shape[:3]) != (C, 3, 3) or G % 8 or not 8 <= G <= 64 or C % G \
+            or int(stride) not in (1, 2):
+        raise ValueError(f"gconv3: w must be [C, 3, 3, G] with G % 8 == 0, 8 <= G <= 64, C % G == 0 "
+                         f"and the stride 1 or 2, got w={tuple(w.shape)}, C={C}, stride={stride}")
+    return C // G
+
+
+def gconv3_fwd(x: Tensor, w: Tensor, stride: int, shift: Optional[Tensor] = None):
+    """Grouped 3 x 3, pad 1, stride 1 / 2, no bias: x [N, H, W, C], w [C, 3, 3, G] (``gconv``'s
+    operand layout, G = C / groups) -> (y, ps, pss); with ``shift`` [C] ps / pss [1, C] are
+    :func:`chan_stats` of the STORED y (BatchNorm's shifted sums), else None."""
+    groups = _gc3_args(w, x.shape[-1], stride)
+    y = F.conv2d(_f(_nchw(x)), _f(_w_oihw(w)), None, stride=int(stride), padding=1, groups=groups)
+    y = _nhwc(y).to(x.dtype)
+    if shift is None:
+        return y, None, None
+    return (y,) + chan_stats(y, shift)
+
+
+def gconv3_dgrad(dy: Tensor, w: Tensor, x_shape, stride: int,
+                 addend: Optional[Tensor] = None) -> Tensor:
+    """dx [N, H, W, C] of :func:`gconv3_fwd` (+ ``addend`` in fp32 before the single rounding)."""
+    N, H, W, C = x_shape
+    groups = _gc3_args(w, C, stride)
+    dx = _nhwc(torch.nn.grad.conv2d_input((N, C, H, W), _f(_w_oihw(w)), _f(_nchw(dy)),
+                                          stride=int(stride), padding=1, groups=groups))
+    if addend is not None:
+        dx = dx + _f(addend)
+    return dx.to(dy.dtype)
+
+
+def gconv3_wgrad(dy: Tensor, x: Tensor, G: int, stride: int) -> Tensor:
+    """dw [C, G, 3, 3] in fp32 (fp64 inputs stay fp64)."""
+    C = x.shape[-1]
+    return torch.nn.grad.conv2d_weight(_f(_nchw(x)), (C, G, 3, 3), _f(_nchw(dy)),
+                                       stride=int(stride), padding=1, groups=C // G)
+
+
 def drop_path_keep(n: int, p: float, seed: int, device="cpu") -> Tensor:
     """[n] keep mask of stochastic depth in "row" mode: the dropout hash (:func:`dropout_keep`)
     applied to the sample index, so it depends only on (seed, sample)."""

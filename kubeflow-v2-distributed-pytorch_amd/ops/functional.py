@@ -1420,6 +1420,54 @@ def dwconvk(x: Tensor, weight: Tensor, w_c: Tensor, stride: int,
                             None if stats_shift is None else stats_shift.detach(), res_give)
 
 
+class _GConv3Fn(Function):
+    """Grouped 3x3 (group width 8 ... 64) at stride 1 / 2 on the MFMA kernels of gconv3.hip, with
+    BatchNorm's shifted statistics from the forward pass.  The data-grad adds a gradient handed
+    over through ``res_give``; the weight gradient accumulates straight into the flat DDP gradient
+    buffer when the parameter lives there (fixed-order sums: no float atomics in any mode)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, w_c, stride, shift, res_give):
+        y, ps, pss = K.gconv3_fwd(x, w_c, stride, shift)
+        ctx.save_for_backward(x, w_c)
+        ctx.weight, ctx.stride, ctx.res_give = weight, stride, res_give
+        ctx.mark_non_differentiable(*[t for t in (ps, pss) if t is not None])
+        return y, ps, pss
+
+    @staticmethod
+    def backward(ctx, dy, _g1, _g2):
+        x, w_c = ctx.saved_tensors
+        weight, stride = ctx.weight, ctx.stride
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            add = ctx.res_give.take() if ctx.res_give is not None else None
+            if add is not None:
+                add = add.reshape(x.shape).to(dy.dtype)
+            dx = K.gconv3_dgrad(dy, w_c, x.shape, stride, add)
+        if ctx.needs_input_grad[1]:
+            tw = _direct_grad_target(weight) if K.use_native(dy) else None
+            # (the flat view keeps the parameter's channels-last strides: passed as it is)
+            g_w = K.gconv3_wgrad(dy, x, w_c.shape[-1], stride, None if tw is None else tw[1])
+            if tw is not None:
+                tw[0].grad_ready(weight)
+            else:
+                dw = g_w.reshape(weight.shape).to(weight.dtype)
+        return dx, dw, None, None, None, None
+
+
+def gconv3(x: Tensor, weight: Tensor, w_c: Tensor, stride: int,
+           stats_shift: Optional[Tensor] = None, res_give: Optional["ResidualSlot"] = None):
+    """``(y, ps, pss)``: grouped 3 x 3, pad 1, stride 1 / 2, no bias, on NHWC ``x``; ``weight``
+    [C, G, 3, 3]: the parameter (gradient target), ``w_c`` [C, 3, 3, G]: the compute-dtype operand
+    (G = C / groups, G % 8 == 0, 8 <= G <= 64).  With ``stats_shift`` (fp32 [C], BatchNorm's
+    running mean) ps / pss are the shifted sums :func:`bn_stats_from_partials` consumes, from the
+    same pass.  ``res_give``: x is also a residual whose gradient was given to the slot; this
+    layer's data-grad adds it."""
+    return _GConv3Fn.apply(x.contiguous(), weight, w_c, int(stride),
+                           None if stats_shift is None else stats_shift.detach(), res_give)
+
+
 def dwconv7(x: Tensor, weight: Tensor, w_c: Tensor, bias: Optional[Tensor],
             res_give: Optional["ResidualSlot"] = None) -> Tensor:
     """Depthwise 7x7, stride 1, pad 3 on NHWC ``x``; ``weight`` [C, 1, 7, 7] / ``bias``: the

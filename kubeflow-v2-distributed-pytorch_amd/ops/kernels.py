@@ -29,6 +29,7 @@ __all__ = ["conv_fwd", "conv_fwd_infer", "bn_fold_affine", "conv_dgrad", "conv_w
            "bn_generic_bwd_reduce", "bn_generic_bwd_apply", "avgpool2d_fwd", "avgpool2d_bwd",
            "dwconv7_fwd", "dwconv7_dgrad", "dwconv7_wgrad", "drop_path_keep",
            "dwconvk_fwd", "dwconvk_dgrad", "dwconvk_wgrad",
+           "gconv3_fwd", "gconv3_dgrad", "gconv3_wgrad",
            "scale_residual_fwd", "scale_residual_bwd",
            "bn_act_pool_fwd", "bn_act_pool_bwd_reduce", "bn_act_pool_bwd_apply", "se_scale_fwd",
            "se_scale_bwd", "window_attention_fwd", "window_attention_bwd", "patch_merge",
@@ -1007,6 +1008,40 @@ def dwconvk_wgrad(dy, x, k, stride, dw=None):
     if use_native(dy):
         return native().dwconvk_wgrad(dy, x, int(k), int(stride), dw)
     g_w = _ref.dwconvk_wgrad(dy, x, k, stride)
+    if dw is not None:
+        dw.add_(g_w.reshape(dw.shape).to(dw.dtype))
+        return None
+    return g_w
+
+
+# ----------------------------------------------------------------------------- gconv3.hip
+def gconv3_fwd(x, w, stride, shift=None):
+    """Grouped 3 x 3, pad 1, stride 1 / 2, no bias, on NHWC ``x``: ``w`` [C, 3, 3, G] in x's dtype
+    (:func:`gconv_fwd`'s operand, read as it stands; G = C / groups) -> (y, ps, pss).  With
+    ``shift`` (fp32 [C]) ps / pss [1, C] are :func:`chan_stats` of the stored y, summed in the same
+    pass in a fixed order, else None.  Native (MFMA): bf16, G % 8 == 0, 8 <= G <= 64."""
+    if use_native(x):
+        return native().gconv3_fwd(x, w, int(stride), shift)
+    return _ref.gconv3_fwd(x, w, stride, shift)
+
+
+def gconv3_dgrad(dy, w, x_shape, stride, addend=None):
+    """dx [N, H, W, C] of :func:`gconv3_fwd`; ``addend`` (dx's shape and dtype) is added in fp32
+    before the single rounding."""
+    if use_native(dy):
+        return native().gconv3_dgrad(dy, w, list(x_shape), int(stride),
+                                     None if addend is None else addend.contiguous())
+    return _ref.gconv3_dgrad(dy, w, x_shape, stride, addend)
+
+
+def gconv3_wgrad(dy, x, G, stride, dw=None):
+    """-> dw [C, G, 3, 3] fp32, ACCUMULATED into ``dw`` (returned as None) when given: C*G*9
+    floats in that order, or a [C, G, 3, 3] tensor, contiguous or channels-last (the parameter's
+    flat-gradient view).  Native: one launch, per-block partial slabs summed in a fixed
+    order: no float atomics, the same bits on every launch, in every mode."""
+    if use_native(dy):
+        return native().gconv3_wgrad(dy, x, int(G), int(stride), dw)
+    g_w = _ref.gconv3_wgrad(dy, x, G, stride)
     if dw is not None:
         dw.add_(g_w.reshape(dw.shape).to(dw.dtype))
         return None
